@@ -2,7 +2,7 @@
 """Headline benchmark: train images/sec of the CIFAR-10-shaped ViT (32x32, patch 4, d=192, L=6,
 H=6, --pos_encoding rope-axial theta=100, bf16) on N MI355X, synthetic data resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: one process per GPU over RCCL.  Started plainly (`python bench.py --gpus 8`, WORLD_SIZE unset) the script
 launches `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py ...` ITSELF, before anything
@@ -11,10 +11,19 @@ torch.distributed.run it just runs as the rank it is.
 
 A "step" = zero_grad -> forward -> mean CE -> backward -> [RCCL all-reduce] -> AdamW on one per-GPU batch of 512
 images (weak scaling: global batch = 512*N; BASELINE.json config 4 is 512/GPU at N=8).  Rank 0 prints ONE JSON line
-with `roofline` (the fused attention forward kernel in the variant the step runs -- LayerNorm fused, xn side output --
-timed live with HIP events over launches that rotate through the six layers' buffers), `other_kernels` (same for the
-other heavy kernels), `cpu_baseline` (the CPU oracle's train step on the host cores; N=1 only) and, for N > 1,
-`n_ranks_seen`, `comm_ms` (event-timed all-reduce of both gradient buckets) and `overlap_frac`.
+with the headline figure (`value` images/sec, `ms_per_step` of the K timed steps) and, for N > 1, `n_ranks_seen`.
+A plain run does nothing else: set-up, W warm-up steps, K timed steps, the outputs, the line.
+
+`--dump-outputs DIR` writes what the last timed step computed (see dump_outputs) as DIR/<name>.npy.  That step starts
+from the seeded weights, AdamW state and batch the run began with, so two builds can be compared output for output --
+within the step's own run-to-run spread: its bf16 kernels are not bit-reproducible (about 1 % of the logits' and
+moments' maximum between two runs of one build; weights within 2 x lr).
+
+`--full` adds the measurements that take runs of their own: `roofline` (the fused attention forward kernel in the
+variant the step runs -- LayerNorm fused, xn side output -- timed live with HIP events over launches that rotate through
+the six layers' buffers), `other_kernels` (same for the other heavy kernels), `cpu_baseline` (the CPU oracle's train
+step on the host cores; N=1 only) and, for N > 1, `comm_ms` (event-timed all-reduce of both gradient buckets) and
+`overlap_frac`.  --no-kernel-probes / --no-cpu-baseline leave out their part of it.
 
 `--dry-run` exercises the launcher / rendezvous / JSON plumbing on CPU ranks (gloo) without a GPU.
 """
@@ -59,7 +68,14 @@ def parse(argv=None):
                          "0 = RCCL's default, or whatever NCCL_MAX_NCHANNELS the caller exported")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU ranks over gloo with a stand-in step: checks launcher, rendezvous and the JSON contract only")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the per-kernel roofline probes, the CPU baseline and (N > 1) the exchange timing")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ launcher
@@ -194,6 +210,35 @@ def cpu_baseline(pos_encoding, steps=60, warmup=2, bs=128, cfg_kw=None, img=32):
                       f"{dt:.1f} s, os.cpu_count()={os.cpu_count()}"}
 
 
+# ------------------------------------------------------------------------------------------------ outputs
+DUMP_MAX_ELEMS = 4 << 20    # per flat buffer (16 MB of float32): the whole dump stays under 64 MB at every geometry
+
+
+def _sample(flat, n_max):
+    """`flat` itself, or a fixed, seeded sample of n_max of its elements (sorted indices, the same in every run)."""
+    if flat.numel() <= n_max:
+        return flat
+    idx = torch.randint(0, flat.numel(), (n_max,), generator=torch.Generator().manual_seed(0)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(eng, out_dir, dry):
+    """What the timed path hands its caller after the last timed step (run from the seeded initial state, see main), as
+    out_dir/<name>.npy (float32): `params`, `adam_m`, `adam_v` = the flat fp32 master weights and AdamW moments the step
+    updated (the step zeroes its own gradient buffer; adam_m is (1 - beta1) x the gradient), `logits` [B, classes] and
+    `loss_correct` = [loss, #correct] of the batch.  A flat buffer longer than DUMP_MAX_ELEMS (the ViT-B/16 geometry) is
+    written as a fixed, seeded sample of its elements."""
+    import numpy as np
+    if dry:
+        arrays = {"w": eng.w}
+    else:
+        arrays = {"params": _sample(eng.flat_p, DUMP_MAX_ELEMS), "adam_m": _sample(eng.flat_m, DUMP_MAX_ELEMS),
+                  "adam_v": _sample(eng.flat_v, DUMP_MAX_ELEMS), "logits": eng.logits, "loss_correct": eng.out2}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
+
+
 # ------------------------------------------------------------------------------------------------ dry run (CPU, gloo)
 class DryEngine:
     """Stand-in for TrainEngine on a CPU rank: same step / exchange structure (two gradient buckets), no model."""
@@ -202,7 +247,7 @@ class DryEngine:
         self.dist, self.world, self.pg = dist, world, None
         self.flat_g = torch.ones(2_677_834)
         self.bucket_off = 1_300_000
-        self.w = torch.randn(256, 256)
+        self.w = torch.randn(256, 256, generator=torch.Generator().manual_seed(0))
 
     def step(self, exchange=True):
         self.w = torch.tanh(self.w @ self.w) * 0.5
@@ -276,12 +321,27 @@ def main(argv=None):
         dist.all_reduce(ones)
         n_ranks_seen = int(round(float(ones.item())))
 
-    def timed_steps(n, exchange=True):
+    # --dump-outputs: the last timed step starts again from the seeded state the run began with, so that what it computes
+    # depends neither on --steps / --warmup nor on the drift of the steps before it (the weight-gradient kernels sum in
+    # fp32 atomics, and AdamW on one resident batch turns those last-bit differences into different weights within a
+    # few hundred steps).  A device-side copy of the weights and AdamW state: tens of microseconds in the timed window.
+    seeded = None
+    if args.dump_outputs and not dry:
+        seeded = [t.clone() for t in (eng.flat_p, eng.flat_m, eng.flat_v, eng.hp)]
+
+    def restore_seeded():
+        for t, s in zip((eng.flat_p, eng.flat_m, eng.flat_v, eng.hp), seeded):
+            t.copy_(s)
+        eng.sync_from_model()     # the bf16 / transposed / packed weight shadows from the restored fp32 masters
+
+    def timed_steps(n, exchange=True, before_last=None):
         if world > 1:
             dist.barrier()
         sync()
         t0 = time.perf_counter()
-        for _ in range(n):
+        for i in range(n):
+            if before_last is not None and i == n - 1:
+                before_last()
             eng.step(exchange=exchange)
         if world > 1:
             dist.barrier()
@@ -295,14 +355,16 @@ def main(argv=None):
 
     for _ in range(args.warmup):
         eng.step()
-    elapsed = timed_steps(args.steps)
+    elapsed = timed_steps(args.steps, before_last=restore_seeded if seeded is not None else None)
     loss = (0.0, 0.0) if dry else eng.read_metrics()
+    if args.dump_outputs and rank == 0:     # before anything below reuses the engine's buffers
+        dump_outputs(eng, args.dump_outputs, dry)
 
     comm_ms = overlap_frac = None
     if world > 1:
         if dry:
             comm_ms, overlap_frac = 0.0, None
-        else:
+        elif args.full:
             comm_ms = time_comm(eng, dist)
             nocomm = timed_steps(args.steps, exchange=False)     # the same step without the exchange (replicas diverge)
             exposed_ms = max(0.0, 1e3 * (elapsed - nocomm) / args.steps)
@@ -313,7 +375,7 @@ def main(argv=None):
 
     peak = BF16_MFMA_PEAK_TFLOPS if args.dtype == "bf16" else F32_MFMA_PEAK_TFLOPS
     recs = []
-    if not dry and rank == 0 and not args.no_kernel_probes:
+    if args.full and not dry and rank == 0 and not args.no_kernel_probes:
         recs = kernel_records(eng, args, peak)
     if world > 1:
         dist.barrier()
@@ -350,7 +412,7 @@ def main(argv=None):
             line["roofline"] = {k: head[k] for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic")}
             line["roofline"].update({k: v for k, v in head.items() if k not in line["roofline"] and k != "name"})
             line["other_kernels"] = [r for r in recs if r["name"] != "attn_fwd"]
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dry:
             line["cpu_baseline"] = (cpu_baseline(args.pos_encoding, steps=20, warmup=1, bs=8, cfg_kw=geom, img=img) if imnet
                                     else cpu_baseline(args.pos_encoding))
         print(json.dumps(line), flush=True)

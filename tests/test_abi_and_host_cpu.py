@@ -271,6 +271,30 @@ def test_bench_refuses_a_world_size_that_contradicts_gpus():
     assert rc != 0 and not lines
 
 
+def test_bench_plain_run_is_lean_and_dumps_the_same_outputs_every_run(tmp_path):
+    """A plain run prints the headline line only (no per-kernel probes, no CPU baseline: those are --full), --steps is
+    the number of timed steps, and --dump-outputs writes the last step's arrays as float32 .npy, identical across runs
+    with the same arguments (seeded inputs)."""
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        rc, lines, err = _run_bench(["--gpus", "1", "--steps", "4", "--warmup", "1", "--dry-run", "--dump-outputs", str(out)])
+        assert rc == 0, err[-2000:]
+        assert len(lines) == 1
+        ln = lines[0]
+        assert ln["steps"] == 4 and ln["warmup"] == 1 and ln["ms_per_step"] > 0
+        assert not {"roofline", "other_kernels", "cpu_baseline"} & set(ln)
+        files = sorted(os.listdir(out))
+        assert files and all(f.endswith(".npy") for f in files)
+        arrs = {f: np.load(out / f) for f in files}
+        assert all(a.dtype == np.float32 for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys()
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+    rc, lines, err = _run_bench(["--gpus", "1", "--steps", "0", "--dry-run"])
+    assert rc != 0 and not lines
+
+
 def test_train_py_refuses_unsupported_geometries_up_front():
     """Every flag of the reference CLI is kept; combinations the attention kernels are not compiled for are refused by
     get_args() with the supported set, the others pass."""

@@ -503,3 +503,43 @@ def test_engine_fragment_packed_shadows_match_the_pack_entry_point_and_the_per_l
     for n in g1:
         if float(g1[n].abs().max()) > 0:
             assert rel_err(g2[n].numpy(), g1[n].numpy()) < 3e-2, n
+
+
+def test_bench_plain_run_dumps_the_last_steps_outputs(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` on the device: one lean result line (the per-kernel probes and
+    the CPU baseline are --full), K timed steps, and the last step's weights, AdamW moments, logits and [loss, #correct]
+    as finite float32 arrays.  That step runs from the seeded initial state, so two runs with different K and W dump the
+    same step, up to the step's own run-to-run spread: its bf16 kernels are not bit-reproducible (the same forward on the
+    same inputs moves the logits by up to ~8e-3 of their maximum from call to call; measured 0.7 % on logits and adam_m,
+    1.4 % on adam_v between runs), and AdamW's first update is +-lr for any gradient clear of eps, so a weight whose
+    gradient is within that noise of zero may move the other way (two learning rates).  Without the reset the two dumps
+    would be different steps (a loss of ~2.2 against ~0.2 after 200 steps)."""
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    names = ("params", "adam_m", "adam_v", "logits", "loss_correct")
+    dumps = []
+    for steps, warmup in ((3, 2), (5, 1)):
+        d = tmp_path / f"s{steps}w{warmup}"
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                              "--warmup", str(warmup), "--dump-outputs", str(d)], cwd=REPO, env=env, capture_output=True,
+                             text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        rep = json.loads(lines[0])
+        assert rep["steps"] == steps and rep["warmup"] == warmup and rep["ms_per_step"] > 0 and rep["value"] > 0
+        assert rep["dtype"] == "bf16" and rep["unit"] == "images/sec" and rep["higher_is_better"] is True
+        assert not {"roofline", "other_kernels", "cpu_baseline"} & set(rep)
+        arrs = {n: np.load(d / (n + ".npy")) for n in names}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert arrs["logits"].shape == (512, 10) and arrs["params"].shape == arrs["adam_m"].shape == arrs["adam_v"].shape
+        assert np.abs(arrs["adam_m"]).max() > 0 and 0 <= arrs["loss_correct"][1] <= 512
+        dumps.append(arrs)
+    a, b = dumps
+    assert rel_err(a["logits"], b["logits"]) <= 3e-2
+    assert abs(float(a["loss_correct"][0]) - float(b["loss_correct"][0])) <= 1e-3
+    assert abs(float(a["loss_correct"][1]) - float(b["loss_correct"][1])) <= 3
+    assert rel_err(a["adam_m"], b["adam_m"]) <= 3e-2 and rel_err(a["adam_v"], b["adam_v"]) <= 5e-2
+    assert np.abs(a["params"].astype(np.float64) - b["params"]).max() <= 2.5e-3

@@ -121,7 +121,7 @@ def test_bench_two_rank_code_path_rehearsal():
         env.pop(k, None)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--no-kernel-probes"], cwd=REPO, env=env, capture_output=True, text=True, timeout=420)
+                          "--full", "--no-kernel-probes"], cwd=REPO, env=env, capture_output=True, text=True, timeout=420)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]      # rank 0 prints ONE JSON line
