@@ -114,7 +114,9 @@ int vitpe_fused_attention_bwd_ln(int dtype, const void* x, const float* gamma, c
  *   qkv  [B,N,3*H*HD] T  output of the qkv Linear (vitpe_linear), columns [q|k|v] x heads x HD
  *   out  [B,N,H*HD]   T  merged heads ; dqkv same layout as qkv
  * PE operands and gradient accumulation as for vitpe_fused_attention_*.  Supported:
- * vitpe_attention_core_supported() -- (HD=64, 193<=N<=208: 224x224 / patch 16) and (HD=32, 65<=N<=80);
+ * vitpe_attention_core_supported() -- HD in {24, 32, 48, 64, 96, 128} (24 / 48 on 32- / 64-wide padded tiles) and
+ * ceil(N/16) in {2, 4, 5, 10, 13, 17} (N = 17, 50, 65, 145..160, 197, 257..272), except where the backward's two LDS tiles
+ * exceed 160 KB: bf16 HD=128 at 17 tiles, fp32 HD=96 at >= 13 tiles, fp32 HD=128 at >= 10 tiles;
  * rope-mixed needs H <= 16.  Anything else returns hipErrorNotSupported.                         */
 int vitpe_attention_core_supported(int dtype, int N, int HD);
 int vitpe_attention_core_fwd(int dtype, const void* qkv, void* out, int B, int N, int H, int HD, int mode,

@@ -327,15 +327,52 @@ def gen_model(ref):
     print("model.npz", len(out), "arrays")
 
 
+# head dimensions 24 / 48 (d = 192 at H = 8 / 4) and 128 (d = 384, H = 3): (tag, extra, embed_dim, num_heads)
+HEADS_MODELS = [(tag, extra, 192, H) for H in (8, 4) for tag, extra in
+                (("rope-mixed", {}), ("relative", {}),
+                 ("polynomial_perhead", {"pos_encoding": "polynomial", "poly_shared_heads": False}))] + \
+               [("rope-axial", {}, 384, 3)]
+HEADS_QKV_ROWS = slice(3, None, 16)   # rows of the qkv-weight gradient kept: every head of q, k and v has some
+
+
+def gen_heads(ref):
+    """Depth-1 models at the head counts of HEADS_MODELS (B = 2, closed-form weights): logits, loss, the gradients of the
+    positional parameters and a row sample of the gradient of blocks.0.attn.qkv.weight (tests/test_head_dims_gpu.py)."""
+    out = {}
+    for tag, extra, D, H in HEADS_MODELS:
+        cfg = mode_cfg(tag, extra, embed_dim=D, depth=1, num_heads=H)
+        model = build_ref_model(ref, cfg)
+        images, labels = O.closed_form_batch(cfg, 2)
+        logits = model(images)
+        loss = nn.CrossEntropyLoss()(logits, labels)
+        loss.backward()
+        key = f"d{D}_h{H}/{tag}"
+        out[f"{key}/logits"], out[f"{key}/loss"] = np_(logits), np_(loss)
+        for k, p in model.named_parameters():
+            if k.startswith("pos_embed."):
+                out[f"{key}/grad/{k}"] = np_(p.grad)
+        g = model.blocks[0].attn.qkv.weight.grad
+        rows = np.arange(g.shape[0])[HEADS_QKV_ROWS]
+        out[f"{key}/qkv_rows"] = rows.astype(np.int64)
+        out[f"{key}/grad_rows/blocks.0.attn.qkv.weight"] = np_(g[torch.from_numpy(rows)])
+    np.savez_compressed(os.path.join(OUT, "heads.npz"), **out)
+    print("heads.npz", {k: v.shape for k, v in out.items()})
+
+
 def main():
     assert os.path.isdir(REF), "reference not present: this script runs in the build container only"
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
     ref = load_reference()
+    if sys.argv[1:] == ["--only", "heads"]:   # leaves the other fixtures byte-identical
+        gen_heads(ref)
+        print("heads.npz", os.path.getsize(os.path.join(OUT, "heads.npz")), "bytes")
+        return
     gen_tables(ref)
     gen_rotary(ref)
     gen_attention(ref)
     gen_model(ref)
+    gen_heads(ref)
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)), "bytes")
 

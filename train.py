@@ -80,10 +80,16 @@ def check_geometry(parser, args):
                 spans[-1][1] = n
             else:
                 spans.append([n, n])
+        # (at the fewest tokens every compiled head dimension fits; the widest heads in fp32 stop at fewer tokens)
+        hds = [d for d in range(1, 513) if h.vitpe_attention_core_supported(dt, ok[0], d)]
+        here = [d for d in hds if h.vitpe_attention_core_supported(dt, n_tok, d)]
+        also = (f"; at {n_tok} tokens in {'fp32' if args.fp32 else 'bf16'}: head dimensions "
+                + ", ".join(map(str, here)) if n_tok in ok and here != hds else "")
         parser.error(f"no attention kernel for {n_tok} tokens (img {args.img_size} / patch {args.patch_size}) with head "
                      f"dimension {hd} (--embed_dim {args.embed_dim} / --num_heads {args.num_heads}): supported head "
-                     f"dimensions 32 and 64, token counts " + ", ".join(f"{a}-{b}" for a, b in spans) +
-                     " (e.g. 32/8 -> 17, 28/4 -> 50, 32/4 -> 65, 224/16 -> 197, 64/4 -> 257)")
+                     f"dimensions " + ", ".join(map(str, hds[:-1])) + f" and {hds[-1]}, token counts " +
+                     ", ".join(f"{a}-{b}" for a, b in spans) +
+                     " (e.g. 32/8 -> 17, 28/4 -> 50, 32/4 -> 65, 224/16 -> 197, 64/4 -> 257)" + also)
     if args.pos_encoding == 'polynomial' and not 0 <= args.poly_degree <= 7:
         parser.error("--poly_degree must be in 0..7 (the attention kernels tabulate the polynomial up to degree 7)")
 

@@ -115,6 +115,9 @@ VITPE_DEV float row16_sum_lane15(float v) {
 //   dfreq[0][hs][f] += (ps % grid) * dph ,  dfreq[1][hs][f] += (ps / grid) * dph   (x scale).
 // The 16 tokens of a tile map to at most (15*H)/P + 2 consecutive hs values: for each candidate the row is reduced
 // with DPP adds and ONE lane per row issues the LDS atomic (the per-lane atomics were 16-way same-address conflicts).
+// FMASK (padded head dimensions, attn_core.h PadMap): lanes whose features f0 + r lie past `half` hold padding and issue no
+// atomic.
+template <bool FMASK = false>
 VITPE_DEV void mixed_freq_grad_tile(float* s_dfreq, const f32x4& dph, int tok, bool tok_ok, int tok0, int h, int H, int P,
                                     int grid, int half, int f0, float scale, int lane) {
   const int c = lane & 15;
@@ -130,7 +133,7 @@ VITPE_DEV void mixed_freq_grad_tile(float* s_dfreq, const f32x4& dph, int tok, b
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float sx = row16_sum_lane15(mx * dph[r]), sy = row16_sum_lane15(my * dph[r]);
-      if (c == 15) {
+      if (c == 15 && (!FMASK || f0 + r < half)) {
         atomicAdd(&s_dfreq[(0 * H + hsv) * half + f0 + r], sx);
         atomicAdd(&s_dfreq[(1 * H + hsv) * half + f0 + r], sy);
       }
