@@ -126,6 +126,20 @@ int vitpe_attention_core_bwd(int dtype, const void* qkv, const void* dout, void*
                              int HD, int mode, const float* cos, const float* sin, const float* table,
                              const float* coeff, int grid, int degree, int coeff_per_head, float* dtable,
                              float* dcoeff, float* dfreqs, vitpe_stream_t stream);
+/* vitpe_attention_core_bwd_tables: vitpe_attention_core_bwd under RoPE with the CALLER's tables (mode rope-axial: cos / sin
+ * [P,HD/2]; rope-mixed: [H,P,HD/2]), which also returns their gradients -- the autograd of the reference's rotation
+ * w.r.t. cos and sin as independent inputs (models/rope_utils.py:3-37, models/vit.py:51-68): per rotate-half pair
+ * (x1, x2) of q and of k with upstream gradient (g1, g2) w.r.t. the rotated pair,
+ *   dcos[.., p, j] += g1 x1 + g2 x2 ,  dsin[.., p, j] += g2 x1 - g1 x2 ,
+ * summed over the batch, q and k (and the heads for a 2-D table) in a fixed order: bit-reproducible, no float atomics.
+ * dcos / dsin (shape of cos / sin) are ACCUMULATED.  dqkv is bitwise what vitpe_attention_core_bwd writes; dfreqs and the
+ * other PE-gradient arguments are ignored.  workspace: 4*B*H*(N-1)*(HD/2) floats (the per-(q/k, image, head) partial
+ * slabs), clobbered.  Same supported shapes as vitpe_attention_core_bwd.                                                */
+int vitpe_attention_core_bwd_tables(int dtype, const void* qkv, const void* dout, void* dqkv, int B, int N, int H,
+                                    int HD, int mode, const float* cos, const float* sin, const float* table,
+                                    const float* coeff, int grid, int degree, int coeff_per_head, float* dtable,
+                                    float* dcoeff, float* dfreqs, float* dcos, float* dsin, float* workspace,
+                                    vitpe_stream_t stream);
 /* vitpe_attention_fused64_fwd: the reference's Attention.forward before self.proj (models/vit.py:47-88) at the ViT-B/16
  * geometry (BASELINE config 5: hd = 64, N = 197) as ONE kernel -- the head's slice of the qkv projection, the rotation /
  * bias, QK^T, softmax and .V per (image, head); q and k never leave the chip.  xn [B,N,D] T = LayerNorm1's output
@@ -314,6 +328,14 @@ int vitpe_rope_mixed_tables_bwd(const float* freqs, const float* dcos, const flo
 /* models/rope_utils.py:3-37 on x [B,H,P,HD] fp32 (called once for q, once for k)              */
 int vitpe_apply_rotary(const float* x, float* y, const float* cosv, const float* sinv, int B, int H,
                        int P, int HD, int per_head, vitpe_stream_t stream);
+/* backward of vitpe_apply_rotary (autograd of models/rope_utils.py:3-37, cos and sin independent inputs): dy, x, dx
+ * [B,H,P,HD] fp32, dx = the transposed rotation of dy (dx1 = g1 c + g2 s, dx2 = g2 c - g1 s; NULL to skip);
+ * dcos / dsin [P,HD/2] or [H,P,HD/2] (per_head) ACCUMULATE g1 x1 + g2 x2 / g2 x1 - g1 x2 summed over B (and H for a
+ * shared table) in a fixed order (NULL to skip; q and k can share one output).  workspace (needed with dcos / dsin):
+ * 2*S*T floats, T = (per_head ? H : 1)*P*(HD/2), S = min(R, 64), R = per_head ? B : B*H.                              */
+int vitpe_apply_rotary_bwd(const float* dy, const float* x, const float* cosv, const float* sinv, float* dx,
+                           float* dcos, float* dsin, float* workspace, int B, int H, int P, int HD, int per_head,
+                           vitpe_stream_t stream);
 
 /* ---- classifier head + loss (vit.py:284-285, train.py:113,119-121,194) -------------------- */
 int vitpe_head_fwd(int dtype, const void* x, const float* gamma, const float* beta, const float* Wh,

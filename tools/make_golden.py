@@ -359,6 +359,67 @@ def gen_heads(ref):
     print("heads.npz", {k: v.shape for k, v in out.items()})
 
 
+# gradients w.r.t. caller-supplied rotary tables (tests/test_rotary_grad_gpu.py): Attention at (d, H), N = 65, B = 2, and
+# apply_rotary_emb on [2, 6, 64, 32].  Closed-form inputs (regenerated by the test), the outputs sampled to keep the file
+# small: tokens RG_TOK of y / dx, rows RG_ROWS[d] of the weight gradients, positions RG_POS of dq / dk.
+RG_GEOMS, RG_B, RG_N = ((96, 3), (192, 8)), 2, 65
+RG_TOK, RG_ROWS, RG_POS = slice(0, None, 8), {96: slice(1, None, 8), 192: slice(1, None, 16)}, slice(0, None, 8)
+
+
+def rotary_grad_tables(kind, shape):
+    """(cos, sin) leaves of the rotary_grad cases: "angle" -> (angle, cos(angle), sin(angle)), a learned-angle table;
+    "free" -> independent cos / sin with cos^2 + sin^2 != 1"""
+    if kind == "angle":
+        ang = (O.closed_form_tensor("rg.angle", shape) * 40).requires_grad_(True)
+        return ang, ang.cos(), ang.sin()
+    cos = (0.8 + O.closed_form_tensor("rg.cos", shape) * 6).requires_grad_(True)
+    sin = (O.closed_form_tensor("rg.sin", shape) * 12).requires_grad_(True)
+    return None, cos, sin
+
+
+def gen_rotary_grad(ref):
+    vit, pe, ru = ref["vit"], ref["positional_encoding"], ref["rope_utils"]
+    out = {"tok": np.arange(RG_N)[RG_TOK], "pos": np.arange(64)[RG_POS]}
+    for D, H in RG_GEOMS:
+        hd, P = D // H, RG_N - 1
+        out[f"d{D}/rows"] = np.arange(3 * D)[RG_ROWS[D]]
+        for kind, shape in (("angle", (P, hd // 2)), ("free", (H, P, hd // 2))):
+            att = vit.Attention(D, num_heads=H)
+            att.set_pos_encoding(pe.RoPEAxial(hd, 100.0) if kind == "angle" else pe.RoPEMixed(hd, H, 100.0))
+            with torch.no_grad():
+                att.qkv.weight.copy_(O.closed_form_tensor("attn.qkv.weight", (3 * D, D)))
+                att.proj.weight.copy_(O.closed_form_tensor("attn.proj.weight", (D, D)))
+                att.proj.bias.copy_(O.closed_form_tensor("attn.proj.bias", (D,)))
+            x = (O.closed_form_tensor("rg.x", (RG_B, RG_N, D)) * 20).requires_grad_(True)
+            dy = O.closed_form_tensor("rg.dy", (RG_B, RG_N, D)) * 20
+            ang, cos, sin = rotary_grad_tables(kind, shape)
+            if ang is not None:
+                cos.retain_grad(), sin.retain_grad()
+            y = att(x, freqs_cis=(cos, sin))
+            y.backward(dy)
+            key = f"d{D}/{kind}"
+            out[f"{key}/y"], out[f"{key}/dx"] = np_(y[:, RG_TOK]), np_(x.grad[:, RG_TOK])
+            out[f"{key}/dwqkv"] = np_(att.qkv.weight.grad[RG_ROWS[D]])
+            out[f"{key}/dwproj"] = np_(att.proj.weight.grad[RG_ROWS[D]])
+            out[f"{key}/dbproj"] = np_(att.proj.bias.grad)
+            out[f"{key}/dcos"], out[f"{key}/dsin"] = np_(cos.grad), np_(sin.grad)
+            if ang is not None:
+                out[f"{key}/dangle"] = np_(ang.grad)
+    q = (O.closed_form_tensor("rotary.q", (2, 6, 64, 32)) * 20).requires_grad_(True)
+    k = (O.closed_form_tensor("rotary.k", (2, 6, 64, 32)) * 20).requires_grad_(True)
+    dq_up = O.closed_form_tensor("rg.dq", (2, 6, 64, 32)) * 20
+    dk_up = O.closed_form_tensor("rg.dk", (2, 6, 64, 32)) * 20
+    for tag, shape in (("shared", (1, 1, 64, 16)), ("per_head", (1, 6, 64, 16))):
+        q.grad = k.grad = None
+        _, cos, sin = rotary_grad_tables("free", shape)
+        qr, kr = ru.apply_rotary_emb(q, k, cos, sin)
+        ((qr * dq_up).sum() + (kr * dk_up).sum()).backward()
+        out[f"rot/{tag}/dq"], out[f"rot/{tag}/dk"] = np_(q.grad[:, :, RG_POS]), np_(k.grad[:, :, RG_POS])
+        out[f"rot/{tag}/dcos"], out[f"rot/{tag}/dsin"] = np_(cos.grad), np_(sin.grad)
+    np.savez_compressed(os.path.join(OUT, "rotary_grad.npz"), **out)
+    print("rotary_grad.npz", {k: v.shape for k, v in out.items()})
+
+
 def main():
     assert os.path.isdir(REF), "reference not present: this script runs in the build container only"
     os.makedirs(OUT, exist_ok=True)
@@ -368,11 +429,16 @@ def main():
         gen_heads(ref)
         print("heads.npz", os.path.getsize(os.path.join(OUT, "heads.npz")), "bytes")
         return
+    if sys.argv[1:] == ["--only", "rotary_grad"]:
+        gen_rotary_grad(ref)
+        print("rotary_grad.npz", os.path.getsize(os.path.join(OUT, "rotary_grad.npz")), "bytes")
+        return
     gen_tables(ref)
     gen_rotary(ref)
     gen_attention(ref)
     gen_model(ref)
     gen_heads(ref)
+    gen_rotary_grad(ref)
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)), "bytes")
 

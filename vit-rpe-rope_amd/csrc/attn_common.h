@@ -32,13 +32,16 @@ struct AttnArgs {
   void* xn_out;
   unsigned long long* census;  // CENSUS instantiation only (vitpe_debug_attn_census): per-wave s_memtime stamps
   void* qkv_out;       // fused hd-64 forward (attn_core.hip): nullable [B,N,3*H*HD] T, the raw projection for the backward
+  float* tab_slab;     // core backward with caller-table gradients (KM_ROPE_TABLES): per-(q/k, image[, head]) partial
+                       // dcos | dsin slabs, written once each (attn_core.h: table_grad_tile)
 };
 
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 
 // kernel-level PE classes (template parameter): what the logits / gradients need
-enum { KM_PLAIN = 0, KM_RELATIVE = 1, KM_POLY = 2, KM_ROPE = 3 };
+// (KM_ROPE_TABLES: the core backward under RoPE that also returns d cos / d sin of the caller's tables)
+enum { KM_PLAIN = 0, KM_RELATIVE = 1, KM_POLY = 2, KM_ROPE = 3, KM_ROPE_TABLES = 4 };
 
 template <typename T, int HD, int D, int MT, int HPP, int NTOK>
 struct AttnCfg {

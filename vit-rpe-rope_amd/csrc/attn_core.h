@@ -304,10 +304,48 @@ __global__ __launch_bounds__(64 * NW) void attn_core_fwd_kernel(AttnArgs a) {
 // =========================================================================================
 constexpr int CORE_HMAX = 16;  // heads, for the RoPE-mixed frequency-gradient scratch
 
+// Gradient w.r.t. the caller's rotary tables of one 16-token tile (KM_ROPE_TABLES; reference rope_utils.py:18-37 under
+// autograd, cos and sin independent inputs).  acc: the [feature][token] accumulators of dq~ (or dk~) BEFORE the rotation
+// back, in the rotary layout (rotate-half partners NT/2 tiles apart, PadMap); gs turns them into the gradient w.r.t. the
+// rotated features, g = gs * acc.  For the pair (x1, x2) = (x[f], x[f + HD/2]) of the raw projection row xrow:
+//   dcos[p][f] = g1 x1 + g2 x2 ,  dsin[p][f] = g2 x1 - g1 x2 ,  p = tok - 1
+// written with plain vector stores into this (q/k, image[, head])'s partial slab -- every (p, f) of the slab exactly once
+// per workgroup -- and summed in a fixed order afterwards (vitpe_attention_core_bwd_tables).  Slab layout: part
+// [2 (q/k)][B] x [cos | sin] x [H][P][HD/2] for 3-D tables (rope-mixed), part [2][B][H] x [cos | sin] x [P][HD/2] for 2-D.
+template <typename T, int HD, int NT>
+VITPE_DEV void table_grad_tile(const AttnArgs& a, const f32x4* acc, const T* xrow, int tok, int qk, int b, int hg, int g,
+                               float gs) {
+  const int N = a.N, P = N - 1;
+  if (tok < 1 || tok >= N) return;   // (class token: not rotated; padding tokens)
+  const bool mixed = a.mode == PE_ROPE_MIXED;
+  const size_t L = (size_t)(mixed ? a.H : 1) * P * (HD / 2);
+  const size_t part = mixed ? (size_t)qk * a.B + b : ((size_t)qk * a.B + b) * a.H + hg;
+  float* dc = a.tab_slab + part * 2 * L + (mixed ? (size_t)hg * P * (HD / 2) : 0) + (size_t)(tok - 1) * (HD / 2);
+  float* ds = dc + L;
+#pragma unroll
+  for (int nt = 0; nt < NT / 2; ++nt) {
+    const int f0 = 16 * nt + 4 * g;
+    if (HD % 32 != 0 && f0 >= HD / 2) continue;   // padded head: positions past HD/2 hold no feature
+    const f32x4 x1 = ld4(xrow + f0), x2 = ld4(xrow + f0 + HD / 2);
+    f32x4 c, s;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float g1 = acc[nt][r] * gs, g2 = acc[nt + NT / 2][r] * gs;
+      c[r] = g1 * x1[r] + g2 * x2[r];
+      s[r] = g2 * x1[r] - g1 * x2[r];
+    }
+    *reinterpret_cast<f32x4*>(dc + f0) = c;
+    *reinterpret_cast<f32x4*>(ds + f0) = s;
+  }
+}
+
 template <typename T, int HD, int MT, int KM, int NW>
 __global__ __launch_bounds__(64 * NW) void attn_core_bwd_kernel(AttnArgs a) {
   using C = AttnCfg<T, (HD + 31) / 32 * 32, (HD + 31) / 32 * 32, MT, 1, 0>;   // (HD = 24 / 48: padded tiles, PadMap)
-  constexpr bool ROPE = (KM == KM_ROPE);
+  // KM_ROPE_TABLES: RoPE with the caller's tables, whose gradients go to a.tab_slab (table_grad_tile) instead of the
+  // RoPE-mixed frequency fold (s_dfreq)
+  constexpr bool TABG = (KM == KM_ROPE_TABLES);
+  constexpr bool ROPE = (KM == KM_ROPE) || TABG;
   // padded head: q~ / k~ / dQ / dK in the rotary layout under RoPE (partners NT/2 tiles apart), cos / sin rows HD/2 wide --
   // the lower-half positions past HD/2 read the row's last four entries (clamped) and produce nothing that is stored
   constexpr bool PAD = HD % 32 != 0;
@@ -319,7 +357,7 @@ __global__ __launch_bounds__(64 * NW) void attn_core_bwd_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) float s_stat[2 * C::NP];  // [lse2 | delta][token]
   __shared__ float s_dtab[KM == KM_RELATIVE ? C::TABLD : 4];
   __shared__ float s_dcoef[C::MAXDEG + 1];
-  __shared__ float s_dfreq[ROPE ? 2 * CORE_HMAX * (HD / 2) : 4];
+  __shared__ float s_dfreq[KM == KM_ROPE ? 2 * CORE_HMAX * (HD / 2) : 4];
 
   const int N = a.N, H = a.H, Dr = H * HD, P = N - 1;
   const int b = blockIdx.x / H, hg = blockIdx.x % H;
@@ -329,8 +367,8 @@ __global__ __launch_bounds__(64 * NW) void attn_core_bwd_kernel(AttnArgs a) {
   const T* qg = reinterpret_cast<const T*>(a.qkv) + (size_t)b * N * 3 * Dr + hg * HD;
   const T* dog = reinterpret_cast<const T*>(a.dout) + (size_t)b * N * Dr + hg * HD;
   T* dq = reinterpret_cast<T*>(a.out) + (size_t)b * N * 3 * Dr + hg * HD;
-  const bool mixed = ROPE && a.mode == PE_ROPE_MIXED;
-  const size_t hoff = mixed ? (size_t)hg * P * (HD / 2) : 0;
+  const bool mixed = KM == KM_ROPE && a.mode == PE_ROPE_MIXED;   // (the frequency fold)
+  const size_t hoff = (ROPE && a.mode == PE_ROPE_MIXED) ? (size_t)hg * P * (HD / 2) : 0;
   const float* cosb = ROPE ? a.cos + hoff : nullptr;
   const float* sinb = ROPE ? a.sin + hoff : nullptr;
   const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
@@ -342,7 +380,7 @@ __global__ __launch_bounds__(64 * NW) void attn_core_bwd_kernel(AttnArgs a) {
   if (KM == KM_RELATIVE)
     for (int q = threadIdx.x; q < C::TABLD; q += NTH) s_dtab[q] = 0.f;
   for (int q = threadIdx.x; q <= C::MAXDEG; q += NTH) s_dcoef[q] = 0.f;
-  if (ROPE)
+  if (KM == KM_ROPE)
     for (int q = threadIdx.x; q < 2 * CORE_HMAX * (HD / 2); q += NTH) s_dfreq[q] = 0.f;
   __syncthreads();
 
@@ -470,6 +508,8 @@ __global__ __launch_bounds__(64 * NW) void attn_core_bwd_kernel(AttnArgs a) {
         mixed_freq_grad_tile<PAD>(s_dfreq, dph, i, tok_ok, 16 * it, hg, H, P, a.grid, HD / 2, 16 * nt + 4 * g, LN2, lane);
       }
     }
+    // dL/d rot(q) = scale * dq~ (q~ = scale*log2e*rot(q), dqa carries 1/log2e: the scale the dQ store applies)
+    if (TABG) table_grad_tile<T, HD, C::NT>(a, dqa, qg + (size_t)il * 3 * Dr, i, 0, b, hg, g, a.scale);
     if (ROPE && i >= 1 && i < N) {
 #pragma unroll
       for (int nt = 0; nt < C::NT / 2; ++nt) {
@@ -588,6 +628,7 @@ __global__ __launch_bounds__(64 * NW) void attn_core_bwd_kernel(AttnArgs a) {
         mixed_freq_grad_tile<PAD>(s_dfreq, dph, j, tok_ok, 16 * jt, hg, H, P, a.grid, HD / 2, 16 * nt + 4 * g, 1.0f, lane);
       }
     }
+    if (TABG) table_grad_tile<T, HD, C::NT>(a, dka, qg + Dr + (size_t)jl * 3 * Dr, j, 1, b, hg, g, 1.0f);   // (LN2 applied)
     if (ROPE && j >= 1 && j < N) {
 #pragma unroll
       for (int nt = 0; nt < C::NT / 2; ++nt) {
@@ -651,7 +692,10 @@ static int launch_core(bool bwd, const AttnArgs& a, hipStream_t s) {
     case PE_RELATIVE: VITPE_CORE_LAUNCH(KM_RELATIVE); break;
     case PE_POLY: VITPE_CORE_LAUNCH(KM_POLY); break;
     case PE_ROPE_AXIAL:
-    case PE_ROPE_MIXED: VITPE_CORE_LAUNCH(KM_ROPE); break;
+    case PE_ROPE_MIXED:
+      if (bwd && a.tab_slab) hipLaunchKernelGGL((attn_core_bwd_kernel<T, HD, MT, KM_ROPE_TABLES, NWB>), grid, dim3(64 * NWB), 0, s, a);
+      else VITPE_CORE_LAUNCH(KM_ROPE);
+      break;
     default: VITPE_CORE_LAUNCH(KM_PLAIN); break;
   }
 #undef VITPE_CORE_LAUNCH

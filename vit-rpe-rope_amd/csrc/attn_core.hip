@@ -370,3 +370,30 @@ extern "C" int vitpe_attention_core_bwd(int dtype, const void* qkv, const void* 
   a.scale = 1.0f / sqrtf((float)HD);
   return dispatch_core(true, dtype, HD, a, stream);
 }
+
+// The core backward with the gradients w.r.t. the caller's rotary tables (rope-axial: 2-D [P, HD/2]; rope-mixed: 3-D
+// [H, P, HD/2]): attn_core_bwd_kernel<KM_ROPE_TABLES> writes every (q/k, image[, head])'s contribution into a partial
+// slab (workspace), reduce_parts sums the slabs in a fixed order into dcos / dsin (accumulated).  dqkv is what
+// vitpe_attention_core_bwd computes; dfreqs is not touched (the tables are not rebuilt from frequencies here).
+extern "C" int vitpe_attention_core_bwd_tables(int dtype, const void* qkv, const void* dout, void* dqkv, int B, int N, int H,
+                                               int HD, int mode, const float* cos, const float* sin, const float* table,
+                                               const float* coeff, int grid, int degree, int coeff_per_head, float* dtable,
+                                               float* dcoeff, float* dfreqs, float* dcos, float* dsin, float* workspace,
+                                               hipStream_t stream) {
+  VITPE_REQUIRE(qkv && dout && dqkv && B >= 0 && N >= 2 && H >= 1);
+  VITPE_REQUIRE(mode == PE_ROPE_AXIAL || mode == PE_ROPE_MIXED);
+  VITPE_REQUIRE(core_check_pe(mode, cos, sin, table, coeff, N, H, grid, degree));
+  VITPE_REQUIRE(dcos && dsin && workspace);
+  (void)dtable; (void)dcoeff; (void)dfreqs;
+  if (B == 0) return 0;
+  AttnArgs a{};
+  a.qkv = qkv; a.dout = dout; a.out = dqkv; a.cos = cos; a.sin = sin;
+  a.tab_slab = workspace;
+  a.B = B; a.N = N; a.H = H; a.mode = mode; a.grid = grid; a.degree = degree; a.coeff_per_head = coeff_per_head;
+  a.scale = 1.0f / sqrtf((float)HD);
+  const int e = dispatch_core(true, dtype, HD, a, stream);
+  if (e) return e;
+  const bool mixed = mode == PE_ROPE_MIXED;
+  const long long L = (long long)(mixed ? H : 1) * (N - 1) * (HD / 2);
+  return reduce_parts(workspace, mixed ? 2 * B : 2 * B * H, L, dcos, dsin, stream);
+}

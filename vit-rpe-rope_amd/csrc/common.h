@@ -305,6 +305,12 @@ VITPE_DEV void gelu_erf_grad_mul_x8(float* v, const float* uv) {
 // positional-encoding modes (include/vitpe.h VITPE_PE_*)
 enum { PE_NONE = 0, PE_ABSOLUTE = 1, PE_RELATIVE = 2, PE_POLY = 3, PE_ROPE_AXIAL = 4, PE_ROPE_MIXED = 5 };
 
+// Deterministic sum of R partial rows (rotary.hip): part [R][2L] fp32, dst0[i] += sum_r part[r][i], dst1[i] += sum_r
+// part[r][L + i] (a null destination is skipped), in a fixed order -- slices of rows summed in place into their first
+// row, then the slices in order.  No float atomics: the result is bit-reproducible.  Clobbers part.
+__attribute__((visibility("hidden"))) int reduce_parts(float* part, int R, long long L, float* dst0, float* dst1,
+                                                       hipStream_t stream);
+
 }  // namespace vitpe
 
 // error plumbing for the C-ABI: every entry point returns hipError_t as int, never throws

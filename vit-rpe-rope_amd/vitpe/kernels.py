@@ -448,16 +448,29 @@ def attention_fused64_fwd(xn, wqkv_pk, num_heads, pe: PETables, qkv_out=None, ou
     return o
 
 
-def attention_core_bwd(qkv, dout, num_heads, pe: PETables, dtable=None, dcoeff=None, dfreqs=None, out=None):
-    """-> dqkv [B,N,3D]; PE-parameter gradients accumulated into dtable/dcoeff/dfreqs."""
-    require_device(qkv, dout, dtable, dcoeff, dfreqs, out)
+def attention_core_bwd(qkv, dout, num_heads, pe: PETables, dtable=None, dcoeff=None, dfreqs=None, out=None,
+                       dcos=None, dsin=None):
+    """-> dqkv [B,N,3D]; PE-parameter gradients accumulated into dtable/dcoeff/dfreqs.  dcos / dsin (both or neither,
+    fp32, the shape of pe.cos / pe.sin): the gradients w.r.t. the caller's rotary tables are accumulated into them
+    (vitpe_attention_core_bwd_tables; dfreqs is then not touched)."""
+    require_device(qkv, dout, dtable, dcoeff, dfreqs, out, dcos, dsin)
     B, N, D3 = qkv.shape
     HD = D3 // 3 // num_heads
     dqkv = out if out is not None else torch.empty_like(qkv)
-    check(lib().vitpe_attention_core_bwd(dtype_code(qkv.dtype), ptr(qkv), ptr(dout), ptr(dqkv), B, N, num_heads, HD,
-                                         pe.code, ptr(pe.cos), ptr(pe.sin), ptr(pe.table), ptr(pe.coeff), pe.grid,
-                                         pe.degree, int(pe.coeff_per_head), ptr(dtable), ptr(dcoeff), ptr(dfreqs),
-                                         stream_ptr()), "vitpe_attention_core_bwd")
+    if dcos is None and dsin is None:
+        check(lib().vitpe_attention_core_bwd(dtype_code(qkv.dtype), ptr(qkv), ptr(dout), ptr(dqkv), B, N, num_heads, HD,
+                                             pe.code, ptr(pe.cos), ptr(pe.sin), ptr(pe.table), ptr(pe.coeff), pe.grid,
+                                             pe.degree, int(pe.coeff_per_head), ptr(dtable), ptr(dcoeff), ptr(dfreqs),
+                                             stream_ptr()), "vitpe_attention_core_bwd")
+        return dqkv
+    if dcos is None or dsin is None or pe.cos is None or dcos.shape != pe.cos.shape or dsin.shape != pe.sin.shape:
+        raise L.VitpeError("attention_core_bwd: dcos and dsin must both be given, shaped like the rotary tables")
+    _f32(dcos, "dcos"), _f32(dsin, "dsin")
+    ws = torch.empty(4 * B * num_heads * (N - 1) * (HD // 2), dtype=torch.float32, device=qkv.device)
+    check(lib().vitpe_attention_core_bwd_tables(dtype_code(qkv.dtype), ptr(qkv), ptr(dout), ptr(dqkv), B, N, num_heads, HD,
+                                                pe.code, ptr(pe.cos), ptr(pe.sin), None, None, pe.grid, 0, 0, None, None,
+                                                None, ptr(dcos), ptr(dsin), ptr(ws), stream_ptr()),
+          "vitpe_attention_core_bwd_tables")
     return dqkv
 
 
@@ -613,6 +626,27 @@ def apply_rotary(x, cos, sin):
     check(lib().vitpe_apply_rotary(ptr(x), ptr(y), ptr(cos), ptr(sin), B, H, P, HD, int(per_head), stream_ptr()),
           "vitpe_apply_rotary")
     return y
+
+
+def apply_rotary_bwd(dy, x, cos, sin, dcos=None, dsin=None, want_dx=True):
+    """Backward of apply_rotary: -> dx [B,H,P,HD] fp32 (None unless want_dx); the gradients w.r.t. cos / sin ([P,HD/2] or
+    [H,P,HD/2]) are ACCUMULATED into dcos / dsin when given (summed over the batch, and the heads for a 2-D table, in a
+    fixed order).  x is only read for the table gradients."""
+    require_device(dy, x, cos, sin, dcos, dsin)
+    _f32(dy, "dy"), _f32(x, "x"), _f32(dcos, "dcos"), _f32(dsin, "dsin")
+    B, H, P, HD = dy.shape
+    per_head = cos.dim() == 3
+    for t in (dcos, dsin):
+        if t is not None and t.shape != cos.shape:
+            raise L.VitpeError("apply_rotary_bwd: dcos / dsin must be shaped like cos / sin")
+    dx = torch.empty_like(dy) if want_dx else None
+    ws = None
+    if dcos is not None or dsin is not None:
+        R = B if per_head else B * H
+        ws = torch.empty(2 * min(R, 64) * (H if per_head else 1) * P * (HD // 2), dtype=torch.float32, device=dy.device)
+    check(lib().vitpe_apply_rotary_bwd(ptr(dy), ptr(x), ptr(cos), ptr(sin), ptr(dx), ptr(dcos), ptr(dsin), ptr(ws), B, H, P,
+                                       HD, int(per_head), stream_ptr()), "vitpe_apply_rotary_bwd")
+    return dx
 
 
 # ---- head + loss ----------------------------------------------------------------------------

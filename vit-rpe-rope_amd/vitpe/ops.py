@@ -85,14 +85,22 @@ def _fused_ok(xn: Tensor, num_heads: int) -> bool:
 @torch.library.custom_op("vitpe::attention", mutates_args=())
 def attention(xn: Tensor, wqkv: Tensor, wproj: Tensor, bproj: Tensor, resid: Optional[Tensor], num_heads: int,
               mode: int, grid: int, pe_param: Optional[Tensor], inv_freq: Optional[Tensor], degree: int,
-              per_head: bool, cos: Optional[Tensor] = None, sin: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+              per_head: bool, cos: Optional[Tensor] = None, sin: Optional[Tensor] = None,
+              tables_grad: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
     """-> (y, a, qkv).  CIFAR geometry: one fused kernel (qkv never leaves the chip, `qkv` is empty; bf16 at N = 65,
     d = 192, hd = 32: the 32x32-tile kernel); bf16 at hd = 64, N = 197: projection + core in one kernel, `qkv` its side output;
-    other geometries: qkv Linear (panel GEMM) + the per-(image, head) attention core.  cos / sin: caller-supplied rotary tables ([P, hd/2] or [H, P, hd/2]) used instead of the module's own."""
+    other geometries: qkv Linear (panel GEMM) + the per-(image, head) attention core.  cos / sin: caller-supplied rotary tables ([P, hd/2] or [H, P, hd/2]) used instead of the module's own.
+    tables_grad: the caller's tables require grad -- the qkv Linear + core route at every geometry (the fused kernels
+    return no table gradients), so that the backward has `qkv` and runs the core backward with table gradients."""
     dt = xn.dtype
     B, N, D = xn.shape
     t = _pe_tables(mode, grid, pe_param, inv_freq, degree, per_head, cos, sin)
-    if _fused_ok(xn, num_heads):
+    if tables_grad:
+        if cos is None or MODES[mode] not in ("rope-axial", "rope-mixed"):
+            raise L.VitpeError("vitpe::attention: tables_grad needs caller (cos, sin) tables in a rope mode")
+        qkv = K.linear(xn.contiguous().view(B * N, D), _shadow(wqkv, dt), None, epi=L.EPI_BIAS).view(B, N, 3 * D)
+        a = K.attention_core_fwd(qkv, num_heads, t)
+    elif _fused_ok(xn, num_heads):
         if K.fused_attention_wide_supported(dt, N, D, D // num_heads):
             a = K.fused_attention_fwd_wide(xn.contiguous(), K.pack_qkv_weights_wide(wqkv.contiguous(), dt, num_heads), num_heads, t)
         else:
@@ -116,21 +124,22 @@ def attention(xn: Tensor, wqkv: Tensor, wproj: Tensor, bproj: Tensor, resid: Opt
 
 
 @attention.register_fake
-def _(xn, wqkv, wproj, bproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos=None, sin=None):
+def _(xn, wqkv, wproj, bproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos=None, sin=None,
+      tables_grad=False):
     B, N, D = xn.shape
     return torch.empty_like(xn), torch.empty_like(xn), xn.new_empty(0)
 
 
 def _attn_setup(ctx, inputs, output):
-    xn, wqkv, wproj, bproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos, sin = inputs
+    xn, wqkv, wproj, bproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos, sin, tables_grad = inputs
     _, a, qkv = output
     ctx.save_for_backward(xn, wqkv, wproj, a, qkv, pe_param, inv_freq, cos, sin)
-    ctx.meta = (num_heads, mode, grid, degree, per_head, resid is not None)
+    ctx.meta = (num_heads, mode, grid, degree, per_head, resid is not None, tables_grad)
 
 
 def _attn_backward(ctx, dy, _da, _dqkv):
     xn, wqkv, wproj, a, qkv, pe_param, inv_freq, cos, sin = ctx.saved_tensors
-    num_heads, mode, grid, degree, per_head, has_resid = ctx.meta
+    num_heads, mode, grid, degree, per_head, has_resid, tables_grad = ctx.meta
     dt = xn.dtype
     B, N, D = xn.shape
     dy2 = dy.contiguous().view(B * N, D)
@@ -148,7 +157,12 @@ def _attn_backward(ctx, dy, _da, _dqkv):
     if cos is not None and name == "rope-mixed":   # caller-supplied tables are constants: the kernel's frequency gradient is discarded
         pe_grads["dfreqs"] = torch.zeros(2, num_heads, D // num_heads // 2, dtype=torch.float32, device=xn.device)
         dpe = None
-    if qkv.numel() == 0:
+    dcos = dsin = None
+    if tables_grad:   # gradients w.r.t. the caller's tables (vitpe_attention_core_bwd_tables), fp32 like t.cos / t.sin
+        dcos, dsin = torch.zeros_like(t.cos), torch.zeros_like(t.sin)
+        dqkv = K.attention_core_bwd(qkv, da.view(B, N, D), num_heads, t, dcos=dcos, dsin=dsin)
+        dcos, dsin = dcos.view(cos.shape).to(cos.dtype), dsin.view(sin.shape).to(sin.dtype)
+    elif qkv.numel() == 0:
         dqkv = K.fused_attention_bwd(xn.contiguous(), K.pack_qkv_weights(wqkv.contiguous(), dt, num_heads),
                                      da.view(B, N, D), num_heads, t, **pe_grads)
     else:
@@ -157,7 +171,7 @@ def _attn_backward(ctx, dy, _da, _dqkv):
     dxn = K.linear(dq2, _shadow_t(wqkv, dt), None, epi=L.EPI_BIAS).view(B, N, D)
     dwqkv = torch.zeros_like(wqkv)
     K.gemm_tn(dq2, xn.contiguous().view(B * N, D), dwqkv, None)
-    return (dxn, dwqkv, dwproj, dbproj, dy if has_resid else None, None, None, None, dpe, None, None, None, None, None)
+    return (dxn, dwqkv, dwproj, dbproj, dy if has_resid else None, None, None, None, dpe, None, None, None, dcos, dsin, None)
 
 
 attention.register_autograd(_attn_backward, setup_context=_attn_setup)

@@ -15,7 +15,7 @@ import torch.nn as nn
 from . import ops  # noqa: F401  (registers torch.ops.vitpe.*)
 from ._lib import VitpeError, require_device
 from .positional_encoding import (AbsolutePositionalEncoding, NoPositionalEncoding, PolynomialRPE,
-                                  RelativePositionalEncoding, RoPEAxial, RoPEMixed)
+                                  RelativePositionalEncoding, RoPEAxial, RoPEMixed, _MixedTables)
 
 _MODE = {"none": 0, "absolute": 1, "relative": 2, "polynomial": 3, "rope-axial": 4, "rope-mixed": 5}
 
@@ -77,6 +77,7 @@ class Attention(nn.Module):
         mode, pe_param, inv_freq, degree, per_head = _pe_args(self.pos_encoding, freqs_cis is not None)
         grid = int(math.sqrt(N - 1))
         cos = sin = None
+        tables_grad = False
         if isinstance(freqs_cis, (tuple, list)) and len(freqs_cis) == 2 and all(torch.is_tensor(t) for t in freqs_cis):
             cos, sin = freqs_cis
             if not (cos.is_cuda and sin.is_cuda):
@@ -87,18 +88,29 @@ class Attention(nn.Module):
                     or (cos.dim() == 3 and cos.shape[0] != self.num_heads):
                 # (reshape_for_broadcast's error, reference rope_utils.py:39-66)
                 raise ValueError(f"Unexpected shape for freqs_cis: {tuple(cos.shape)}")
-            if cos.requires_grad or sin.requires_grad:
-                # autograd-tracked tables are RoPEMixed.get_freqs_cis of the module's own frequencies (reference
-                # vit.py:262-266): the kernel rebuilds them from the parameter, so the gradient reaches it as the
-                # reference's autograd would; differentiable tables from anywhere else are not supported
-                if not isinstance(self.pos_encoding, RoPEMixed) or cos.dim() != 3:
-                    raise NotImplementedError("vitpe Attention: caller-supplied (cos, sin) tables that require grad")
+            if (cos.requires_grad or sin.requires_grad) and self._own_mixed_tables(cos, sin):
+                # RoPEMixed.get_freqs_cis of this module's own frequencies (reference vit.py:262-266): the kernel
+                # rebuilds the tables from the parameter and sends the gradient there, as the reference's autograd would
                 cos = sin = None
             else:
+                # constant tables, or differentiable ones from anywhere else: used as given; the latter take the
+                # qkv Linear + core route, whose backward returns d cos / d sin (vitpe::attention, tables_grad)
+                tables_grad = torch.is_grad_enabled() and (cos.requires_grad or sin.requires_grad)
                 mode, pe_param, inv_freq = (_MODE["rope-axial"] if cos.dim() == 2 else _MODE["rope-mixed"]), None, None
         y, _, _ = torch.ops.vitpe.attention(x, self.qkv.weight, self.proj.weight, self.proj.bias, resid, self.num_heads,
-                                         mode, grid, pe_param, inv_freq, degree, per_head, cos, sin)
+                                         mode, grid, pe_param, inv_freq, degree, per_head, cos, sin, tables_grad)
         return y
+
+    def _own_mixed_tables(self, cos, sin):
+        """Are (cos, sin) provably RoPEMixed.get_freqs_cis of this module's own `freqs` (one _MixedTables node whose
+        input is the parameter itself)?"""
+        pe = self.pos_encoding
+        fn = cos.grad_fn
+        if not isinstance(pe, RoPEMixed) or fn is None or sin.grad_fn is not fn \
+                or type(fn) is not _MixedTables._backward_cls:
+            return False
+        src = fn.next_functions[0][0] if fn.next_functions else None
+        return src is not None and getattr(src, "variable", None) is pe.freqs
 
     def set_pos_encoding(self, pos_encoding):
         self.pos_encoding = pos_encoding
