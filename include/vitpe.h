@@ -280,6 +280,22 @@ int vitpe_layernorm_bwd(int dtype, const void* dy, const void* x, const float* m
 int vitpe_reduce_partials(const float* partial, int nparts, int len0, int len1, float* dst0,
                           float* dst1, vitpe_stream_t stream);
 
+/* ---- transforms.Resize (train.py:69-70,78-79) -------------------------------------------------
+ * Resize(S) on the square uint8 images of datasets.MNIST (mode L) / datasets.CIFAR10 (mode RGB) is PIL's
+ * img.resize((S, S), Image.BILINEAR): per channel plane a horizontal pass to a uint8 intermediate [S0][S], then a
+ * vertical pass, each integer arithmetic on fixed-point coefficients -- reproduced bit for bit.
+ * vitpe_resize_coeffs: PURE HOST.  One pass from length `in` to length `out`: bounds [out][2] = (first source index,
+ * tap count), kk [out][ksize] = round(weight * 2^22) (zero past the tap count); returns ksize = 2 ceil(max(in/out, 1))
+ * + 1, or a negative value (and writes nothing) when ksize_cap < ksize or an argument is invalid.                    */
+int vitpe_resize_coeffs(int in, int out, int* bounds, int* kk, int ksize_cap);
+/* src [planes][S0][S0] -> dst [planes][S][S] uint8, planes = images x channels; the tables are DEVICE copies of
+ * vitpe_resize_coeffs(S0, S) for the horizontal (_h) and vertical (_v) pass, ksize its return value.  S == S0 is a
+ * copy (tables may be NULL).  Supported: S0 in 8..64, S in 4..512; anything else is hipErrorNotSupported.          */
+int vitpe_resize_u8_supported(int S0, int S);
+int vitpe_resize_u8(const unsigned char* src, unsigned char* dst, long long planes, int S0, int S,
+                    const int* bounds_h, const int* kk_h, const int* bounds_v, const int* kk_v, int ksize,
+                    vitpe_stream_t stream);
+
 /* ---- patch embed (vit.py:164,245-258) ------------------------------------------------------- */
 /* img [B,C,S,S] fp32 -> patches [B*P, C*p*p] T, column = c*p*p + ky*p + kx                    */
 int vitpe_unfold(int dtype, const float* img, void* patches, int B, int C, int S, int p,

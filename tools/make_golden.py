@@ -14,6 +14,7 @@ code runs unmodified.  Consequently everything except the Mlp arithmetic is
 pinned by the reference itself; the Mlp boundary is "parity unpinned".
 
 Usage:  python tools/make_golden.py            (writes tests/golden/)
+        python tools/make_golden.py --only resize     (resize.npz alone, from PIL; also heads, rotary_grad)
 """
 import importlib.util
 import os
@@ -420,7 +421,93 @@ def gen_rotary_grad(ref):
     print("rotary_grad.npz", {k: v.shape for k, v in out.items()})
 
 
+# --------------------------------------------------------------------------- resize.npz
+# transforms.Resize(S) of reference train.py:70,79 on the square PIL images of datasets.MNIST (mode L) and
+# datasets.CIFAR10 (mode RGB) is, by torchvision's documented behaviour, img.resize((S, S), Image.BILINEAR) (PIL always
+# antialiases).  torchvision is not installed in the build container, so that mapping is taken from its documentation
+# and could not be confirmed by running it; what the fixture pins is PIL's resize itself.
+RESIZE_CASES = {"mnist": (1, 28, (14, 16, 32, 64, 224)), "cifar": (3, 32, (16, 24, 48, 64, 224))}
+
+
+def resize_pass_coeffs(size_in, size_out):
+    """PIL's 8-bit bilinear coefficients of one pass, restated independently of PIL (Python floats are IEEE doubles,
+    one operation per expression): -> (bounds int32 [out,2], kk int32 [out,ksize])."""
+    import math
+    scale = size_in / size_out
+    fs = max(scale, 1.0)
+    support = 1.0 * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    bounds = np.zeros((size_out, 2), dtype=np.int32)
+    kk = np.zeros((size_out, ksize), dtype=np.int32)
+    for xx in range(size_out):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        n = min(int(center + support + 0.5), size_in) - xmin
+        w = []
+        for x in range(n):
+            t = abs((x + xmin - center + 0.5) / fs)
+            w.append(1.0 - t if t < 1.0 else 0.0)
+        ww = 0.0
+        for v in w:
+            ww += v
+        for x in range(n):
+            kk[xx, x] = int(w[x] / ww * float(1 << 22) + 0.5)
+        bounds[xx] = (xmin, n)
+    return bounds, kk
+
+
+def resize_apply(planes, bounds, kk):
+    """One pass along the last axis by the integer formula: clip((2^21 + sum in[xmin + x] * k[x]) >> 22)."""
+    idx = np.minimum(bounds[:, :1] + np.arange(kk.shape[1])[None], planes.shape[-1] - 1)   # taps past n weigh 0
+    acc = (planes[..., idx].astype(np.int64) * kk.astype(np.int64)).sum(-1) + (1 << 21)
+    return np.clip(acc >> 22, 0, 255).astype(np.uint8)
+
+
+def resize_inputs(rng, n, C, S0):
+    """n images [n,C,S0,S0] uint8: random bytes, a 0/255 checkerboard (clip and rounding half-way points), a smooth
+    ramp, random again."""
+    x = rng.integers(0, 256, (n, C, S0, S0), dtype=np.uint8)
+    yy, xx = np.mgrid[0:S0, 0:S0]
+    if n > 1:
+        for c in range(C):
+            x[1, c] = (((yy + xx + c) % 2) * 255).astype(np.uint8)
+    if n > 2:
+        for c in range(C):
+            x[2, c] = ((yy * (c + 1) + xx * (3 - c)) * 255 // ((S0 - 1) * 4)).astype(np.uint8)
+    return x
+
+
+def gen_resize():
+    from PIL import Image
+    rng = np.random.default_rng(20261016)
+    out = {}
+    for name, (C, S0, sizes) in RESIZE_CASES.items():
+        for S in sizes:
+            n = 2 if S == 224 else 4
+            x = resize_inputs(rng, n, C, S0)
+            y = np.zeros((n, C, S, S), dtype=np.uint8)
+            for i in range(n):
+                if C == 1:
+                    y[i, 0] = np.asarray(Image.fromarray(x[i, 0], "L").resize((S, S), Image.BILINEAR))
+                else:
+                    hwc = np.ascontiguousarray(x[i].transpose(1, 2, 0))
+                    y[i] = np.asarray(Image.fromarray(hwc, "RGB").resize((S, S), Image.BILINEAR)).transpose(2, 0, 1)
+            bounds, kk = resize_pass_coeffs(S0, S)
+            mid = resize_apply(x, bounds, kk)                                        # horizontal -> [n,C,S0,S]
+            mine = resize_apply(mid.transpose(0, 1, 3, 2), bounds, kk).transpose(0, 1, 3, 2)   # vertical
+            assert np.array_equal(mine, y), f"{name} {S0}->{S}: the restated coefficients do not reproduce PIL"
+            key = f"{name}/{S}"
+            out[f"{key}/x"], out[f"{key}/y"], out[f"{key}/bounds"], out[f"{key}/kk"] = x, y, bounds, kk
+    np.savez_compressed(os.path.join(OUT, "resize.npz"), **out)
+    print("resize.npz", {k: v.shape for k, v in out.items() if k.endswith("/y")})
+
+
 def main():
+    if sys.argv[1:] == ["--only", "resize"]:   # PIL only: the reference's modules are not needed; the others stay as they are
+        os.makedirs(OUT, exist_ok=True)
+        gen_resize()
+        print("resize.npz", os.path.getsize(os.path.join(OUT, "resize.npz")), "bytes")
+        return
     assert os.path.isdir(REF), "reference not present: this script runs in the build container only"
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
@@ -439,6 +526,7 @@ def main():
     gen_model(ref)
     gen_heads(ref)
     gen_rotary_grad(ref)
+    gen_resize()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)), "bytes")
 

@@ -6,7 +6,8 @@ in equal contiguous slices of the permutation.
 
 Readers for the datasets' own binary formats (no pickle): CIFAR-10 "binary version" (data_batch_{1..5}.bin,
 test_batch.bin: 1 label byte + 3072 pixel bytes, channel-planar) and MNIST idx files
-({train,t10k}-images-idx3-ubyte, -labels-idx1-ubyte; 28x28 is resized to 32x32 once at load time).
+({train,t10k}-images-idx3-ubyte, -labels-idx1-ubyte).  The records are uploaded at their native size (32x32 / 28x28)
+and transforms.Resize(img_size) runs once on the device (kernels.resize_u8: PIL's bilinear resample, bit for bit).
 """
 from __future__ import annotations
 
@@ -57,9 +58,11 @@ def _read_idx(path: str) -> np.ndarray:
 
 
 def read_mnist_idx(root: str, train: bool, img_size: int = 32) -> Tuple[np.ndarray, np.ndarray]:
-    """-> (images uint8 [N,1,S,S], labels int64 [N]).  transforms.Resize(img_size) (bilinear, on the uint8 image,
-    train.py:70) is applied once here; torchvision / PIL are absent from the build image, so the resize is torch's
-    bilinear (half-pixel centres) rounded to uint8 -- parity with PIL's fixed-point resize is unpinned (+-1 LSB)."""
+    """-> (images uint8 [N,1,S,S], labels int64 [N]).  A host-side reader for callers without a device: img_size 28
+    returns the records as they are; any other size goes through torch's bilinear interpolate (half-pixel centres, no
+    antialiasing) rounded to uint8, which is NOT the reference's transforms.Resize -- against PIL it is off by one level
+    on about a fifth of the pixels at upscales and wrong at downscales.  ResidentDataset.from_files does not use this
+    path: it reads at 28 and resizes on the device with kernels.resize_u8, which reproduces PIL exactly."""
     pre = "train" if train else "t10k"
     x = _read_idx(os.path.join(root, f"{pre}-images-idx3-ubyte"))
     y = _read_idx(os.path.join(root, f"{pre}-labels-idx1-ubyte")).astype(np.int64)
@@ -90,18 +93,28 @@ class ResidentDataset:
     def __len__(self):
         return self.images.shape[0]
 
+    def resized(self, img_size: int) -> "ResidentDataset":
+        """transforms.Resize(img_size) (reference train.py:70,79) applied once to the whole resident set on the device;
+        the same labels and normalisation constants.  The native-size images are released with `self`."""
+        if int(img_size) == self.images.shape[-1]:
+            return self
+        from . import kernels as K
+        with torch.cuda.device(self.device):
+            images = K.resize_u8(self.images, img_size)
+        return ResidentDataset(images, self.labels, self.mean.tolist(), self.std.tolist(), self.device)
+
     @classmethod
     def from_files(cls, dataset: str, root: str, train: bool, device="cuda", img_size: int = 32):
+        """The dataset's binary files -> resident uint8 set at img_size: uploaded at the native size, resized on the
+        device (both datasets)."""
         if dataset == "cifar10":
             x, y = read_cifar10_bin(root, train)
-            if img_size != 32:
-                raise VitpeError("cifar10 binary records are 32x32; other --img_size values need a resize pass")
         elif dataset == "mnist":
-            x, y = read_mnist_idx(root, train, img_size)
+            x, y = read_mnist_idx(root, train, 28)
         else:
             raise VitpeError(f"unknown dataset {dataset}")
         mean, std = DATASET_STATS[dataset]
-        return cls(x, y, mean, std, device)
+        return cls(x, y, mean, std, device).resized(img_size)
 
 
 def shard_slice(n_items: int, rank: int, world: int) -> Tuple[int, int]:

@@ -501,6 +501,49 @@ def unfold_u8(data, index, mean, std, patch, dtype, out=None, img_out=None):
     return o
 
 
+def resize_coeffs(size_in: int, size_out: int):
+    """Coefficient tables of one pass of PIL's 8-bit bilinear resample from length size_in to size_out (host only):
+    -> (bounds int32 [out,2] = (first source index, tap count), kk int32 [out,ksize] = round(weight * 2^22))."""
+    size_in, size_out = int(size_in), int(size_out)
+    if size_in < 1 or size_out < 1:
+        raise L.VitpeError(f"resize_coeffs: sizes must be positive (got {size_in} -> {size_out})")
+    ksize = 2 * -(-max(size_in, size_out) // size_out) + 1      # 2 ceil(max(in / out, 1)) + 1
+    bounds = torch.zeros((size_out, 2), dtype=torch.int32)
+    kk = torch.zeros((size_out, ksize), dtype=torch.int32)
+    got = lib().vitpe_resize_coeffs(size_in, size_out, bounds.data_ptr(), kk.data_ptr(), ksize)
+    if got != ksize:
+        raise L.VitpeError(f"vitpe_resize_coeffs({size_in}, {size_out}) returned {got}, expected ksize {ksize}")
+    return bounds, kk
+
+
+def resize_u8_supported(S0: int, S: int) -> bool:
+    return bool(lib().vitpe_resize_u8_supported(int(S0), int(S)))
+
+
+def resize_u8(images_u8, S: int, out=None):
+    """transforms.Resize(S) on a device uint8 tensor [N,C,S0,S0] -> [N,C,S,S]: PIL's Image.resize((S, S), BILINEAR),
+    bit for bit (S == S0: a copy).  `out` (optional) is a contiguous uint8 device tensor of at least N*C*S*S elements."""
+    require_device(images_u8, out)
+    S = int(S)
+    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[2] != images_u8.shape[3]:
+        raise L.VitpeError("resize_u8: images must be uint8 [N,C,S0,S0] (square)")
+    N, C, S0, _ = images_u8.shape
+    if not resize_u8_supported(S0, S):
+        raise L.VitpeError(f"resize_u8: {S0} -> {S} is not supported (source 8..64, target 4..512)")
+    if out is None:
+        out = torch.empty((N, C, S, S), dtype=torch.uint8, device=images_u8.device)
+    elif out.dtype != torch.uint8 or out.numel() < N * C * S * S:
+        raise L.VitpeError("resize_u8: out must be uint8 with at least N*C*S*S elements")
+    bounds = kk = None
+    ksize = 0
+    if S != S0:
+        bounds, kk = (t.to(images_u8.device) for t in resize_coeffs(S0, S))     # square: both passes share the tables
+        ksize = kk.shape[1]
+    check(lib().vitpe_resize_u8(ptr(images_u8), ptr(out), N * C, S0, S, ptr(bounds), ptr(kk), ptr(bounds), ptr(kk), ksize,
+                                stream_ptr()), "vitpe_resize_u8")
+    return out
+
+
 def patch_embed_supported(dtype, C, S, p, D) -> bool:
     return bool(lib().vitpe_patch_embed_supported(dtype_code(dtype), C, S, p, D))
 
