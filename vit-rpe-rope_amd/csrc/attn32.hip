@@ -65,12 +65,12 @@ VITPE_DEV bf16x8 pack8(const f32x16& a) {
 }
 
 VITPE_DEV bf16x8 ldsfrag(const bf16* p) { return *reinterpret_cast<const bf16x8*>(p); }
-// (fmaxf on matrix-core outputs costs a canonicalising v_max per operand; the logits are finite by construction)
-VITPE_DEV float max3(float a, float b, float c) {
-  float d;
-  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
+// Plain fmaxf, which hipcc folds into one v_max3_f32 (no canonicalising v_max in the ISA).  NOT inline asm: the
+// operands are MFMA results, and the compiler does not insert the MFMA -> VALU wait states (s_nop 11 here) in front of
+// an asm statement -- the v_max3 then read accumulators the matrix core had not written yet, the row maximum depended
+// on timing, and the outputs of the modes without a bias lookup between the MFMAs and the maximum (none, rope) differed
+// by a bf16 ulp from launch to launch.
+VITPE_DEV float max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 // the same LDS address read again in a later phase must be a NEW read: left alone, the compiler keeps all 24 token
 // fragments of the first projection alive for the other two (96 registers) and spills
 VITPE_DEV const bf16* fresh(const bf16* p) { asm volatile("" : "+v"(p)); return p; }
