@@ -153,6 +153,51 @@ int vitpe_attention_fused64_fwd(int dtype, const void* xn, const void* wqkv_pack
                                 const float* table, const float* coeff, int grid, int degree, int coeff_per_head,
                                 vitpe_stream_t stream);
 
+/* ---- dropout ------------------------------------------------------------------------------
+ * The reference's nn.Dropout sites (models/vit.py:36,38 attn_drop / proj_drop, applied at vit.py:85,92; timm Mlp's drop1 /
+ * drop2 behind vit.py:118) and timm's DropPath (vit.py:115, used at vit.py:122,124).  torch draws those masks from its own
+ * generator; here every keep decision is a pure function of (seed, offset, logical element e, p) on Philox4x32-10:
+ *   key = (lo32 seed, hi32 seed) ; counter = (lo32(e >> 2), hi32(e >> 2), lo32 offset, hi32 offset) ; word = e & 3
+ *   keep(e) = word >= floor(p * 2^32) ; kept values are multiplied by 1 / (1 - p)
+ * so a backward regenerates the forward's mask and no mask is ever stored.  `rng` is a DEVICE pointer to the two 64-bit
+ * words (seed, offset), read by the kernels when they run: a captured graph replays with the pair's current contents.
+ * 0 <= p < 1 and rng != NULL, else hipErrorInvalidValue (nothing is launched).
+ *
+ * vitpe_philox4x32_10: host-only, the generator itself (key2[2], ctr4[4] -> out4[4]); same source as the device code.
+ * vitpe_dropout_mask : uint8 keep mask of a site, for tests (the product path never materialises a mask).
+ *   site 0 (elementwise) and 1 (per sample): e = index, mask [n];   site 2 (attention probabilities): mask [B,H,N,N],
+ *   e = ((b H + h) N + i) NP + j with NP = N rounded up to a multiple of 4 (n ignored).
+ * vitpe_dropout_fwd  : y = [resid +] x . m / (1-p), n elements of T, e = element index (resid nullable).
+ * vitpe_dropout_bwd  : dx = dy . m / (1-p) with the same pair.
+ * vitpe_drop_path_fwd: y = [resid +] x * m_b / (1-p), one decision per sample b < B (e = b) of `per` elements each: timm
+ *   DropPath with scale_by_keep=True (third-party code, parity unpinned).  vitpe_drop_path_bwd: dx = dy * m_b / (1-p).  B <= 2^24
+ *   (64 workgroups per sample in one grid dimension), else hipErrorInvalidValue.   */
+int vitpe_philox4x32_10(const unsigned int* key2, const unsigned int* ctr4, unsigned int* out4);
+int vitpe_dropout_mask(int site, const unsigned long long* rng, unsigned char* mask, long long n, int B, int H, int N,
+                       float p, vitpe_stream_t stream);
+int vitpe_dropout_fwd(int dtype, const void* x, const void* resid, void* y, long long n, const unsigned long long* rng,
+                      float p, vitpe_stream_t stream);
+int vitpe_dropout_bwd(int dtype, const void* dy, void* dx, long long n, const unsigned long long* rng, float p,
+                      vitpe_stream_t stream);
+int vitpe_drop_path_fwd(int dtype, const void* x, const void* resid, void* y, int B, long long per,
+                        const unsigned long long* rng, float p, vitpe_stream_t stream);
+int vitpe_drop_path_bwd(int dtype, const void* dy, void* dx, int B, long long per, const unsigned long long* rng, float p,
+                        vitpe_stream_t stream);
+/* vitpe_attention_core_fwd_drop / _bwd_drop: vitpe_attention_core_fwd / _bwd with the reference's attention-probability
+ * dropout (models/vit.py:84-88: softmax -> attn_drop -> @ v) applied to P in registers, site 2 above.  The backward
+ * regenerates the mask in both of its passes: dV from P . m / (1-p), dP = (dO V^T) . m / (1-p).  p == 0 launches exactly
+ * the kernels of vitpe_attention_core_fwd / _bwd (bitwise the same result).  Same supported shapes and PE modes; there is
+ * no dropout variant of vitpe_attention_core_bwd_tables.                                                                */
+int vitpe_attention_core_fwd_drop(int dtype, const void* qkv, void* out, int B, int N, int H, int HD, int mode,
+                                  const float* cos, const float* sin, const float* table, const float* coeff,
+                                  int grid, int degree, int coeff_per_head, const unsigned long long* rng, float p,
+                                  vitpe_stream_t stream);
+int vitpe_attention_core_bwd_drop(int dtype, const void* qkv, const void* dout, void* dqkv, int B, int N, int H,
+                                  int HD, int mode, const float* cos, const float* sin, const float* table,
+                                  const float* coeff, int grid, int degree, int coeff_per_head, float* dtable,
+                                  float* dcoeff, float* dfreqs, const unsigned long long* rng, float p,
+                                  vitpe_stream_t stream);
+
 /* ---- GEMMs ------------------------------------------------------------------------------
  * vitpe_gemm_nt: C[M,N] = epi(A[M,K] W[N,K]^T).  nn.Linear forward (vit.py:35,37; timm Mlp
  * fc1/fc2), nn.Conv2d-as-GEMM patch embed (vit.py:164,248), and -- on a transposed weight

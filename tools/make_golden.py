@@ -502,6 +502,115 @@ def gen_resize():
     print("resize.npz", {k: v.shape for k, v in out.items() if k.endswith("/y")})
 
 
+# ---- dropout.npz: the reference's own Attention / Block arithmetic under GIVEN dropout masks ------------------------------
+# The masks are the project's documented stream (DESIGN.md "Dropout streams", restated in tests/dropout_stream.py) for fixed
+# (seed, offset) pairs; the reference's nn.Dropout modules, the timm stand-in's drop and DropPath are replaced by modules
+# that multiply with those masks, everything else is the reference's vit.py.  Inputs and weights are closed-form (not
+# stored); stored: the pairs, the packed mask bits, outputs and gradients (large weight gradients as a row sample).
+DROP_DIM, DROP_H = 96, 3
+DROP_ATTN_CASES = [("rope-axial", 17, 3), ("relative", 17, 3), ("rope-axial", 65, 2), ("relative", 65, 2)]
+DROP_ATTN_P, DROP_PROJ_P = 0.1, 0.2
+DROP_BLOCK = dict(N=17, B=4, drop=0.1, attn_drop=0.15, drop_path=0.3)
+
+
+class _MaskMul(nn.Module):
+    """x * mask_k on the k-th call (masks already carry 1 / (1 - p))"""
+
+    def __init__(self, *masks):
+        super().__init__()
+        self.masks, self.calls = masks, 0
+
+    def forward(self, x):
+        m = self.masks[self.calls % len(self.masks)]
+        self.calls += 1
+        return x * m
+
+
+def _drop_pairs(tag, n):
+    """n fixed (seed, offset) pairs below 2^63 (torch int64), derived from the case tag"""
+    import hashlib
+    h = hashlib.sha256(tag.encode()).digest()
+    while len(h) < 16 * n:
+        h += hashlib.sha256(h).digest()
+    v = np.frombuffer(h[:16 * n], dtype="<u8").reshape(n, 2) >> np.uint64(1)
+    return [(int(a), int(b)) for a, b in v]
+
+
+def gen_dropout(ref):
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import dropout_stream as S
+    vit, pe = ref["vit"], ref["positional_encoding"]
+    out = {}
+    CF = O.closed_form_tensor
+    f32 = lambda m, p: torch.from_numpy(m.astype(np.float32) * S.scale(p))  # noqa: E731
+    for tag, N, B in DROP_ATTN_CASES:
+        key = f"attn/{tag}/n{N}"
+        pairs = _drop_pairs(key, 2)
+        att = vit.Attention(DROP_DIM, num_heads=DROP_H, qkv_bias=True, attn_drop=DROP_ATTN_P, proj_drop=DROP_PROJ_P)
+        hd = DROP_DIM // DROP_H
+        pem = pe.RelativePositionalEncoding(N - 1, DROP_H) if tag == "relative" else pe.RoPEAxial(hd, 100.0)
+        att.set_pos_encoding(pem)
+        with torch.no_grad():
+            for n, p in att.named_parameters():
+                if not n.startswith("pos_encoding."):
+                    p.copy_(CF("attn." + n, tuple(p.shape)))
+            for n, p in pem.named_parameters():
+                p.copy_(CF("pos_embed." + n, tuple(p.shape)))
+        ma = S.mask_attention(pairs[0], B, DROP_H, N, DROP_ATTN_P)
+        mp = S.mask_elements(pairs[1], B * N * DROP_DIM, DROP_PROJ_P).reshape(B, N, DROP_DIM)
+        att.attn_drop, att.proj_drop = _MaskMul(f32(ma, DROP_ATTN_P)), _MaskMul(f32(mp, DROP_PROJ_P))
+        x = (CF("attn.x", (B, N, DROP_DIM)) * 20).requires_grad_(True)
+        dy = CF("attn.dy", (B, N, DROP_DIM)) * 20
+        freqs_cis = pem.get_freqs_cis(N - 1, torch.device("cpu")) if tag == "rope-axial" else None
+        y = att(x, freqs_cis=freqs_cis)
+        y.backward(dy)
+        out[f"{key}/pairs"] = np.array(pairs, dtype=np.int64)
+        out[f"{key}/mask_attn"], out[f"{key}/mask_proj"] = np.packbits(ma), np.packbits(mp)
+        out[f"{key}/y"], out[f"{key}/dx"] = np_(y), np_(x.grad)
+        out[f"{key}/grad_rows4/qkv.weight"] = np_(att.qkv.weight.grad)[::4]
+        for n in ("qkv.bias", "proj.weight", "proj.bias"):
+            out[f"{key}/grad/{n}"] = np_(dict(att.named_parameters())[n].grad)
+        for n, p in pem.named_parameters():
+            out[f"{key}/grad/pos_encoding.{n}"] = np_(p.grad)
+    c = DROP_BLOCK
+    N, B = c["N"], c["B"]
+    pairs = _drop_pairs("block", 6)      # attention probabilities, proj, drop1, drop2, drop-path (attention), drop-path (MLP)
+    blk = vit.Block(DROP_DIM, DROP_H, qkv_bias=True, drop=c["drop"], attn_drop=c["attn_drop"], drop_path=0.)
+    blk.set_pos_encoding(pe.NoPositionalEncoding())
+    with torch.no_grad():
+        for n, p in blk.named_parameters():
+            p.copy_(CF("blk." + n, tuple(p.shape)))
+    hid = blk.mlp.fc1.weight.shape[0]
+    ma = S.mask_attention(pairs[0], B, DROP_H, N, c["attn_drop"])
+    mp = S.mask_elements(pairs[1], B * N * DROP_DIM, c["drop"]).reshape(B, N, DROP_DIM)
+    m1 = S.mask_elements(pairs[2], B * N * hid, c["drop"]).reshape(B, N, hid)
+    m2 = S.mask_elements(pairs[3], B * N * DROP_DIM, c["drop"]).reshape(B, N, DROP_DIM)
+    da, dm = (S.mask_elements(pairs[k], B, c["drop_path"]).reshape(B, 1, 1) for k in (4, 5))
+    blk.attn.attn_drop, blk.attn.proj_drop = _MaskMul(f32(ma, c["attn_drop"])), _MaskMul(f32(mp, c["drop"]))
+    # timm's Mlp: fc1 -> act -> drop1 -> fc2 -> drop2; timm's DropPath(scale_by_keep=True): x * keep_b / (1 - p) -- both
+    # third-party, restated (parity unpinned); the Block applies ONE DropPath module to both branches (vit.py:115,122,124)
+    d1, d2 = _MaskMul(f32(m1, c["drop"])), _MaskMul(f32(m2, c["drop"]))
+    mlp = blk.mlp
+    mlp.forward = lambda t: d2(mlp.fc2(d1(mlp.act(mlp.fc1(t)))))
+    blk.drop_path = _MaskMul(f32(da, c["drop_path"]), f32(dm, c["drop_path"]))
+    x = (CF("blk.x", (B, N, DROP_DIM)) * 20).requires_grad_(True)
+    dy = CF("blk.dy", (B, N, DROP_DIM)) * 20
+    y = blk(x)
+    y.backward(dy)
+    out["block/pairs"] = np.array(pairs, dtype=np.int64)
+    for n, m in (("attn", ma), ("proj", mp), ("drop1", m1), ("drop2", m2), ("path_attn", da), ("path_mlp", dm)):
+        out[f"block/mask_{n}"] = np.packbits(m)
+    out["block/y"], out["block/dx"] = np_(y), np_(x.grad)
+    rows = {"attn.qkv.weight": 4, "mlp.fc1.weight": 8, "mlp.fc2.weight": 4}
+    for n, p in blk.named_parameters():
+        if n in rows:
+            out[f"block/grad_rows{rows[n]}/{n}"] = np_(p.grad)[::rows[n]]
+        else:
+            out[f"block/grad/{n}"] = np_(p.grad)
+    np.savez_compressed(os.path.join(OUT, "dropout.npz"), **out)
+    print("dropout.npz", {k: v.shape for k, v in out.items()})
+
+
 def main():
     if sys.argv[1:] == ["--only", "resize"]:   # PIL only: the reference's modules are not needed; the others stay as they are
         os.makedirs(OUT, exist_ok=True)
@@ -516,6 +625,10 @@ def main():
         gen_heads(ref)
         print("heads.npz", os.path.getsize(os.path.join(OUT, "heads.npz")), "bytes")
         return
+    if sys.argv[1:] == ["--only", "dropout"]:
+        gen_dropout(ref)
+        print("dropout.npz", os.path.getsize(os.path.join(OUT, "dropout.npz")), "bytes")
+        return
     if sys.argv[1:] == ["--only", "rotary_grad"]:
         gen_rotary_grad(ref)
         print("rotary_grad.npz", os.path.getsize(os.path.join(OUT, "rotary_grad.npz")), "bytes")
@@ -526,6 +639,7 @@ def main():
     gen_model(ref)
     gen_heads(ref)
     gen_rotary_grad(ref)
+    gen_dropout(ref)
     gen_resize()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)), "bytes")

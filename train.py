@@ -56,7 +56,15 @@ def get_args(argv=None):
                         help='directory holding the dataset in its binary format (CIFAR-10 binary batches / MNIST idx '
                              'files); it is loaded once into HBM as uint8 (no download: there is no network here)')
     parser.add_argument('--seed', type=int, default=0, help='seed of the per-epoch shuffle')
+    # model options beyond the reference's CLI (its Block accepts them, its train.py never sets them); all off by default
+    parser.add_argument('--qkv_bias', action='store_true', help='bias on the qkv projection')
+    parser.add_argument('--drop', type=float, default=0.0, help='dropout rate behind attn.proj and inside the MLP')
+    parser.add_argument('--attn_drop', type=float, default=0.0, help='dropout rate on the attention probabilities')
+    parser.add_argument('--drop_path', type=float, default=0.0, help='stochastic depth: rate of the last block')
     args = parser.parse_args(argv)
+    for name in ('drop', 'attn_drop', 'drop_path'):
+        if not 0.0 <= getattr(args, name) < 1.0:
+            parser.error(f"--{name} must be in [0, 1)")
     check_geometry(parser, args)
     return args
 
@@ -202,8 +210,23 @@ def test(engine, loader):
     return loss_sum / max(len(loader), 1), 100. * correct / max(seen, 1)
 
 
+def engine_refusal(args):
+    """The training loop here is the TrainEngine's, whose fused kernels have no qkv bias and no dropout: say so instead of
+    training without what was asked for.  -> message, or None."""
+    active = [f for f, on in (('--qkv_bias', args.qkv_bias), ('--drop', args.drop > 0), ('--attn_drop', args.attn_drop > 0),
+                              ('--drop_path', args.drop_path > 0)) if on]
+    if not active:
+        return None
+    return ("train.py: " + ", ".join(active) + " not supported by the TrainEngine training loop (no qkv bias, no dropout in "
+            "its fused kernels); models.vit.VisionTransformer(..., qkv_bias=, drop_rate=, attn_drop_rate=, drop_path_rate=) "
+            "runs them through the module path (torch autograd over torch.ops.vitpe.*)")
+
+
 def main(argv=None):
     args = get_args(argv)
+    extras = engine_refusal(args)
+    if extras:   # up front: before the dataset is loaded and the device touched
+        raise SystemExit(extras)
     if not torch.cuda.is_available():
         raise SystemExit("train.py needs an MI355X: the HIP path is the only path (no CPU fallback)")
     from vitpe import ddp

@@ -34,6 +34,11 @@ struct AttnArgs {
   void* qkv_out;       // fused hd-64 forward (attn_core.hip): nullable [B,N,3*H*HD] T, the raw projection for the backward
   float* tab_slab;     // core backward with caller-table gradients (KM_ROPE_TABLES): per-(q/k, image[, head]) partial
                        // dcos | dsin slabs, written once each (attn_core.h: table_grad_tile)
+  // attention-probability dropout (attn_core.h, DROP instantiations; philox.h): the (seed, offset) pair in device memory,
+  // the keep threshold floor(p 2^32) and 1 / (1 - p); rng == nullptr: the kernels without dropout
+  const unsigned long long* rng;
+  unsigned drop_thr;
+  float drop_rs;
 };
 
 constexpr float LOG2E = 1.4426950408889634f;

@@ -2,6 +2,7 @@
 // hd-64 forward; attn_core_hd.hip: the padded head dimensions 24 / 48 and 96 / 128, one translation unit each).
 #pragma once
 #include "attn_common.h"
+#include "philox.h"
 #include <type_traits>
 
 namespace vitpe {
@@ -215,10 +216,48 @@ VITPE_DEV void stage_pe(const AttnArgs& a, int hg, float* s_tab, float* s_coef, 
   if (KM == KM_POLY) stage_poly<C>(a, hg, s_coef, N, tid, nthreads);
 }
 
+// ---- attention-probability dropout (reference vit.py:84-88: softmax -> attn_drop -> @ v) -----------------------------------
+// Site element of (image b, head h, query i, key j): e = ((b H + h) N + i) NP4 + j, NP4 = N rounded up to a multiple of 4
+// ("Dropout streams"): the four keys 4 jq .. 4 jq + 3 of one query row are the four words of ONE Philox call,
+// counter row_q + jq with row_q = ((b H + h) N + i) (NP4 / 4).
+struct DropCtx {
+  DropKey key;
+  uint64_t bh_rows;   // (b H + h) N
+  uint32_t nq, thr;
+  float rs;
+};
+VITPE_DEV DropCtx drop_ctx(const AttnArgs& a, int b, int hg) {
+  DropCtx d;
+  d.key = drop_key(a.rng);
+  d.bh_rows = (uint64_t)(b * a.H + hg) * (uint64_t)a.N;
+  d.nq = (uint32_t)(a.N + 3) >> 2;
+  d.thr = a.drop_thr;
+  d.rs = a.drop_rs;
+  return d;
+}
+// swapped S^T tile (lane: query i, keys 16 jt + 4 g + r): the lane's accumulator quad is one Philox call
+VITPE_DEV Philox4 drop_quad(const DropCtx& d, int i, int jq) { return drop_words(d.key, (d.bh_rows + (uint64_t)i) * d.nq + (uint64_t)jq); }
+// plain S tile (lane: key j = 16 jt + c, queries i0 + r, i0 = 16 it + 4 g): the four lanes of a DPP quad hold the keys
+// 4 jq .. 4 jq + 3; lane t of the quad draws query i0 + t's call and packs its four keep bits, a quad broadcast hands every
+// lane the nibble of each query, of which it reads its own key's bit.  -> keep bits of (i0 + r, j) in bit r.  Uniform
+// control flow required (cross-lane reads).
+VITPE_DEV uint32_t drop_keep_T(const DropCtx& d, int i0, int j, int lane) {
+  const int t = lane & 3;
+  const Philox4 w = drop_quad(d, i0 + t, j >> 2);
+  const int nib = (w.w[0] >= d.thr ? 1 : 0) | (w.w[1] >= d.thr ? 2 : 0) | (w.w[2] >= d.thr ? 4 : 0) | (w.w[3] >= d.thr ? 8 : 0);
+  const int n0 = __builtin_amdgcn_update_dpp(0, nib, 0x00, 0xF, 0xF, true);   // quad_perm:[0,0,0,0]
+  const int n1 = __builtin_amdgcn_update_dpp(0, nib, 0x55, 0xF, 0xF, true);   // quad_perm:[1,1,1,1]
+  const int n2 = __builtin_amdgcn_update_dpp(0, nib, 0xAA, 0xF, 0xF, true);   // quad_perm:[2,2,2,2]
+  const int n3 = __builtin_amdgcn_update_dpp(0, nib, 0xFF, 0xF, 0xF, true);   // quad_perm:[3,3,3,3]
+  return (uint32_t)(((n0 >> t) & 1) | (((n1 >> t) & 1) << 1) | (((n2 >> t) & 1) << 2) | (((n3 >> t) & 1) << 3));
+}
+
 // =========================================================================================
 // Forward: NW = MT waves, one query tile each
 // =========================================================================================
-template <typename T, int HD, int MT, int KM, int NW>
+// DROP: attention-probability dropout on P in registers, between the softmax and the accumulator-as-operand P.V -- a
+// compile-time variant: the DROP = false instantiations are the kernels without it
+template <typename T, int HD, int MT, int KM, int NW, bool DROP = false>
 __global__ __launch_bounds__(64 * NW) void attn_core_fwd_kernel(AttnArgs a) {
   using C = AttnCfg<T, (HD + 31) / 32 * 32, (HD + 31) / 32 * 32, MT, 1, 0>;   // (HD = 24 / 48: padded tiles, PadMap)
   constexpr bool ROPE = (KM == KM_ROPE);
@@ -236,6 +275,9 @@ __global__ __launch_bounds__(64 * NW) void attn_core_fwd_kernel(AttnArgs a) {
   const size_t hoff = (ROPE && a.mode == PE_ROPE_MIXED) ? (size_t)hg * P * (HD / 2) : 0;
   const float* cosb = ROPE ? a.cos + hoff : nullptr;
   const float* sinb = ROPE ? a.sin + hoff : nullptr;
+
+  DropCtx dc{};   // (the site's pair and row base: read once per workgroup, wave-uniform)
+  if constexpr (DROP) dc = drop_ctx(a, b, hg);
 
   stage_rows<T, C, ROPE, HD>(a, qg + Dr, 3 * Dr, cosb, sinb, 1.0f, kt, C::NP, threadIdx.x, 64 * NW);
   stage_rows<T, C, false, HD>(a, qg + 2 * Dr, 3 * Dr, nullptr, nullptr, 1.0f, vt, C::VR, threadIdx.x, 64 * NW);
@@ -268,6 +310,14 @@ __global__ __launch_bounds__(64 * NW) void attn_core_fwd_kernel(AttnArgs a) {
         l += p;
       }
     l = xg_sum(l);
+    if constexpr (DROP) {   // the row sum above is the softmax's (all keys); dropped entries leave P.V, 1/(1-p) rides on 1/l
+#pragma unroll
+      for (int jt = 0; jt < MT; ++jt) {
+        const Philox4 w = drop_quad(dc, il, 4 * jt + g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s[jt][r] = w.w[r] >= dc.thr ? s[jt][r] : 0.f;
+      }
+    }
     f32x4 o[C::NT];
 #pragma unroll
     for (int dt = 0; dt < C::NT; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -279,7 +329,7 @@ __global__ __launch_bounds__(64 * NW) void attn_core_fwd_kernel(AttnArgs a) {
       for (int dt = 0; dt < C::NT; ++dt)
         if (tile_live<HD, false>(dt)) mma(ld_frag_tr(vt, C::LDH, 32 * sc + 4 * g, 32 * sc + 16 + 4 * g, 16 * dt), bp, o[dt]);
     }
-    const float inv = __builtin_amdgcn_rcpf(l);
+    const float inv = DROP ? __builtin_amdgcn_rcpf(l) * a.drop_rs : __builtin_amdgcn_rcpf(l);
     if (i < N) {
       if constexpr (sizeof(T) == 2) {
 #pragma unroll
@@ -339,7 +389,9 @@ VITPE_DEV void table_grad_tile(const AttnArgs& a, const f32x4* acc, const T* xro
   }
 }
 
-template <typename T, int HD, int MT, int KM, int NW>
+// DROP: both recomputations of P regenerate the forward's keep mask m (drop_quad / drop_keep_T): dP = (dO V^T) . m / (1-p)
+// in the query-tile jobs, dV from P . m / (1-p) and the same dP in the key-tile jobs; sum_j P_ij dP_ij is still dO_i . O_i
+template <typename T, int HD, int MT, int KM, int NW, bool DROP = false>
 __global__ __launch_bounds__(64 * NW) void attn_core_bwd_kernel(AttnArgs a) {
   using C = AttnCfg<T, (HD + 31) / 32 * 32, (HD + 31) / 32 * 32, MT, 1, 0>;   // (HD = 24 / 48: padded tiles, PadMap)
   // KM_ROPE_TABLES: RoPE with the caller's tables, whose gradients go to a.tab_slab (table_grad_tile) instead of the
@@ -374,6 +426,9 @@ __global__ __launch_bounds__(64 * NW) void attn_core_bwd_kernel(AttnArgs a) {
   const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
   const float qsc = a.scale * LOG2E;
 
+  DropCtx dc{};   // (the site's pair and row base: read once per workgroup, wave-uniform)
+  if constexpr (DROP) dc = drop_ctx(a, b, hg);
+
   stage_rows<T, C, ROPE, HD>(a, qg + Dr, 3 * Dr, cosb, sinb, 1.0f, t0, C::VR, threadIdx.x, NTH);
   stage_rows<T, C, false, HD>(a, qg + 2 * Dr, 3 * Dr, nullptr, nullptr, 1.0f, t1, C::NP, threadIdx.x, NTH);
   stage_pe<C, KM>(a, hg, s_tab, s_coef, threadIdx.x, NTH);
@@ -407,6 +462,14 @@ __global__ __launch_bounds__(64 * NW) void attn_core_bwd_kernel(AttnArgs a) {
 #pragma unroll
       for (int cs = 0; cs < C::HC; ++cs) mma(ld_frag(vrow + 16 * jt * C::LDH + 32 * cs), bdo[cs], dp[jt]);
       if (MT > 8 && (jt & 1)) __builtin_amdgcn_sched_barrier(0);  // bound the load hoisting (register pressure)
+    }
+    if constexpr (DROP) {
+#pragma unroll
+      for (int jt = 0; jt < MT; ++jt) {
+        const Philox4 w = drop_quad(dc, il, 4 * jt + g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dp[jt][r] = w.w[r] >= dc.thr ? dp[jt][r] * dc.rs : 0.f;
+      }
     }
     float l = 0.f;
 #pragma unroll
@@ -584,6 +647,8 @@ __global__ __launch_bounds__(64 * NW) void attn_core_bwd_kernel(AttnArgs a) {
           }
           const f32x4 lse = *reinterpret_cast<const f32x4*>(&s_stat[0 * C::NP + 16 * it + 4 * g]);
           const f32x4 dl = *reinterpret_cast<const f32x4*>(&s_stat[1 * C::NP + 16 * it + 4 * g]);
+          uint32_t keep = 0xFu;
+          if constexpr (DROP) keep = drop_keep_T(dc, 16 * it + 4 * g, j, lane);   // (rows / keys >= N: masked below)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int i = 16 * it + 4 * g + r;
@@ -591,8 +656,14 @@ __global__ __launch_bounds__(64 * NW) void attn_core_bwd_kernel(AttnArgs a) {
             if (KM == KM_RELATIVE || KM == KM_POLY) sv += pe_bias2<C, KM>(a, s_tab, s_coef, 0, i, j, N);
             const bool valid = kvalid && ((it < MT - 1) || (i < N));
             const float pv = valid ? __builtin_amdgcn_exp2f(sv - lse[r]) : 0.f;
-            p[hf][r] = pv;
-            ds[hf][r] = pv * (ds[hf][r] - dl[r]);
+            if constexpr (DROP) {
+              const bool kp = (keep >> r) & 1u;
+              p[hf][r] = kp ? pv * a.drop_rs : 0.f;
+              ds[hf][r] = pv * ((kp ? ds[hf][r] * a.drop_rs : 0.f) - dl[r]);
+            } else {
+              p[hf][r] = pv;
+              ds[hf][r] = pv * (ds[hf][r] - dl[r]);
+            }
           }
         }
       }
@@ -674,32 +745,44 @@ __global__ __launch_bounds__(64 * NW) void attn_core_bwd_kernel(AttnArgs a) {
   }
 }
 
-template <typename T, int HD, int MT>
-static int launch_core(bool bwd, const AttnArgs& a, hipStream_t s) {
+template <typename T, int HD, int MT, bool DROP>
+static int launch_core_v(bool bwd, const AttnArgs& a, hipStream_t s) {
   // forward: one wave per query tile (two rounds above 13 tiles); backward: half as many waves (two rounds) so that
   // the p/dS accumulators of a key-tile job (2*MT f32x4) stay in registers
   // Head dimensions beyond 32 / 64 at 17 tiles: six waves (three rounds, 256 registers a lane) -- at nine waves (168
   // registers) they spilled 14-112 VGPRs (tools/regs.sh attn_core_hd.hip)
-  constexpr bool SIX = HD != 32 && HD != 64 && MT > 13;
+  // The dropout variants at 17 tiles run on six waves at every head dimension: at nine they spilled 10-230 VGPRs
+  constexpr bool SIX = (DROP || (HD != 32 && HD != 64)) && MT > 13;
   constexpr int NWF = SIX ? 6 : (MT > 13) ? (MT + 1) / 2 : MT, NWB = SIX ? 6 : (MT > 8) ? (MT + 1) / 2 : MT;
   const dim3 grid((unsigned)(a.B * a.H));
 #define VITPE_CORE_LAUNCH(KM)                                                                                      \
   do {                                                                                                               \
-    if (bwd) hipLaunchKernelGGL((attn_core_bwd_kernel<T, HD, MT, KM, NWB>), grid, dim3(64 * NWB), 0, s, a);          \
-    else hipLaunchKernelGGL((attn_core_fwd_kernel<T, HD, MT, KM, NWF>), grid, dim3(64 * NWF), 0, s, a);              \
+    if (bwd) hipLaunchKernelGGL((attn_core_bwd_kernel<T, HD, MT, KM, NWB, DROP>), grid, dim3(64 * NWB), 0, s, a);    \
+    else hipLaunchKernelGGL((attn_core_fwd_kernel<T, HD, MT, KM, NWF, DROP>), grid, dim3(64 * NWF), 0, s, a);        \
   } while (0)
   switch (a.mode) {
     case PE_RELATIVE: VITPE_CORE_LAUNCH(KM_RELATIVE); break;
     case PE_POLY: VITPE_CORE_LAUNCH(KM_POLY); break;
     case PE_ROPE_AXIAL:
     case PE_ROPE_MIXED:
-      if (bwd && a.tab_slab) hipLaunchKernelGGL((attn_core_bwd_kernel<T, HD, MT, KM_ROPE_TABLES, NWB>), grid, dim3(64 * NWB), 0, s, a);
-      else VITPE_CORE_LAUNCH(KM_ROPE);
+      if constexpr (!DROP) {   // (table gradients together with dropout: not built, refused by the entry points)
+        if (bwd && a.tab_slab) {
+          hipLaunchKernelGGL((attn_core_bwd_kernel<T, HD, MT, KM_ROPE_TABLES, NWB>), grid, dim3(64 * NWB), 0, s, a);
+          break;
+        }
+      }
+      VITPE_CORE_LAUNCH(KM_ROPE);
       break;
     default: VITPE_CORE_LAUNCH(KM_PLAIN); break;
   }
 #undef VITPE_CORE_LAUNCH
   VITPE_CHECK_LAUNCH();
+}
+// a.rng set: the dropout instantiations; otherwise exactly the kernels without it
+template <typename T, int HD, int MT>
+static int launch_core(bool bwd, const AttnArgs& a, hipStream_t s) {
+  if (a.rng != nullptr) return a.tab_slab ? (int)hipErrorNotSupported : launch_core_v<T, HD, MT, true>(bwd, a, s);
+  return launch_core_v<T, HD, MT, false>(bwd, a, s);
 }
 
 // Instantiated geometries: head dimension 32 / 64 and these token-tile counts MT = ceil(N / 16) -- the square grids the

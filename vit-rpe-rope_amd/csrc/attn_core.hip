@@ -325,6 +325,24 @@ extern "C" int vitpe_attention_core_fwd(int dtype, const void* qkv, void* out, i
   return dispatch_core(false, dtype, HD, a, stream);
 }
 
+// Attention-probability dropout inside the core (reference vit.py:84-88, softmax -> attn_drop -> @ v).  p == 0 launches
+// exactly vitpe_attention_core_fwd's kernels.
+extern "C" int vitpe_attention_core_fwd_drop(int dtype, const void* qkv, void* out, int B, int N, int H, int HD, int mode,
+                                             const float* cos, const float* sin, const float* table, const float* coeff,
+                                             int grid, int degree, int coeff_per_head, const unsigned long long* rng, float p,
+                                             hipStream_t stream) {
+  VITPE_REQUIRE(qkv && out && B >= 0 && N >= 2 && H >= 1);
+  VITPE_REQUIRE(rng && drop_p_ok(p));
+  VITPE_REQUIRE(core_check_pe(mode, cos, sin, table, coeff, N, H, grid, degree));
+  if (B == 0) return 0;
+  AttnArgs a{};
+  a.qkv = qkv; a.out = out; a.cos = cos; a.sin = sin; a.table = table; a.coeff = coeff;
+  a.B = B; a.N = N; a.H = H; a.mode = mode; a.grid = grid; a.degree = degree; a.coeff_per_head = coeff_per_head;
+  a.scale = 1.0f / sqrtf((float)HD);
+  if (p > 0.0f) { a.rng = rng; a.drop_thr = drop_threshold(p); a.drop_rs = drop_scale(p); }
+  return dispatch_core(false, dtype, HD, a, stream);
+}
+
 // The fused forward at hd = 64 (attn_fused64_fwd_kernel): bf16, 193 <= N <= 208 (13 token tiles), H <= 16 heads of 64.
 extern "C" int vitpe_attention_fused64_supported(int dtype, int N, int H, int HD) {
   return dtype == 1 && HD == 64 && (N + 15) / 16 == 13 && H >= 1 && H <= CORE_HMAX;
@@ -368,6 +386,27 @@ extern "C" int vitpe_attention_core_bwd(int dtype, const void* qkv, const void* 
   a.dtable = dtable; a.dcoeff = dcoeff; a.dfreqs = dfreqs;
   a.B = B; a.N = N; a.H = H; a.mode = mode; a.grid = grid; a.degree = degree; a.coeff_per_head = coeff_per_head;
   a.scale = 1.0f / sqrtf((float)HD);
+  return dispatch_core(true, dtype, HD, a, stream);
+}
+
+extern "C" int vitpe_attention_core_bwd_drop(int dtype, const void* qkv, const void* dout, void* dqkv, int B, int N, int H,
+                                             int HD, int mode, const float* cos, const float* sin, const float* table,
+                                             const float* coeff, int grid, int degree, int coeff_per_head, float* dtable,
+                                             float* dcoeff, float* dfreqs, const unsigned long long* rng, float p,
+                                             hipStream_t stream) {
+  VITPE_REQUIRE(qkv && dout && dqkv && B >= 0 && N >= 2 && H >= 1);
+  VITPE_REQUIRE(rng && drop_p_ok(p));
+  VITPE_REQUIRE(core_check_pe(mode, cos, sin, table, coeff, N, H, grid, degree));
+  if (mode == PE_RELATIVE) VITPE_REQUIRE(dtable);
+  if (mode == PE_POLY) VITPE_REQUIRE(dcoeff);
+  if (mode == PE_ROPE_MIXED) VITPE_REQUIRE(dfreqs);
+  if (B == 0) return 0;
+  AttnArgs a{};
+  a.qkv = qkv; a.dout = dout; a.out = dqkv; a.cos = cos; a.sin = sin; a.table = table; a.coeff = coeff;
+  a.dtable = dtable; a.dcoeff = dcoeff; a.dfreqs = dfreqs;
+  a.B = B; a.N = N; a.H = H; a.mode = mode; a.grid = grid; a.degree = degree; a.coeff_per_head = coeff_per_head;
+  a.scale = 1.0f / sqrtf((float)HD);
+  if (p > 0.0f) { a.rng = rng; a.drop_thr = drop_threshold(p); a.drop_rs = drop_scale(p); }
   return dispatch_core(true, dtype, HD, a, stream);
 }
 

@@ -32,9 +32,30 @@ from .vit import VisionTransformer
 ALIGN = 8  # elements: keeps every parameter 32-B (fp32) / 16-B (bf16 shadow) aligned
 
 
+def engine_unsupported(model):
+    """Names of the active model options TrainEngine cannot run (qkv bias, dropout, stochastic depth); [] if none."""
+    active = []
+    for blk in model.blocks:
+        if blk.attn.qkv.bias is not None:
+            active.append("qkv_bias")
+        if blk.attn.attn_drop_p > 0.:
+            active.append("attn_drop")
+        if blk.attn.proj_drop_p > 0. or blk.mlp.drop > 0.:
+            active.append("drop")
+        if blk.drop_path_p > 0.:
+            active.append("drop_path")
+    return sorted(set(active))
+
+
 class TrainEngine:
     def __init__(self, model: VisionTransformer, batch_size: int, compute_dtype=torch.bfloat16, lr=1e-3,
                  weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, process_group=None, use_graph=True, fuse_ln=None):
+        active = engine_unsupported(model)
+        if active:
+            # the flat buffers and fused kernels of this engine have no bias input on the qkv projection and no dropout
+            # (DESIGN.md 8): refuse instead of silently training without them
+            raise NotImplementedError("TrainEngine does not support " + ", ".join(active) + " (the fused training path has "
+                                      "no qkv bias and no dropout); train this model through the module path instead")
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise L.VitpeError("TrainEngine needs the model on the HIP device (no CPU path)")

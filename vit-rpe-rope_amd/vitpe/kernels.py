@@ -474,6 +474,108 @@ def attention_core_bwd(qkv, dout, num_heads, pe: PETables, dtable=None, dcoeff=N
     return dqkv
 
 
+# ---- dropout (csrc/dropout.hip, csrc/philox.h; DESIGN.md "Dropout streams") -----------------------------------------
+SITE_ELEMENT, SITE_SAMPLE, SITE_ATTENTION = 0, 1, 2
+
+
+def new_rng_pairs(n, device):
+    """n (seed, offset) pairs [n, 2] int64 drawn from torch's device generator -- no host sync; torch.manual_seed
+    therefore reproduces them.  The kernels read a pair as two unsigned 64-bit words."""
+    return torch.empty((n, 2), dtype=torch.int64, device=device).random_()
+
+
+def _check_rng(rng):
+    require_device(rng)
+    if rng.dtype != torch.int64 or rng.numel() != 2:
+        raise L.VitpeError("rng must be a contiguous int64 device tensor of two words (seed, offset)")
+
+
+def dropout_mask(rng, p, n=None, attn_shape=None):
+    """uint8 keep mask of a site (tests only): n elements (elementwise / per-sample sites) or attn_shape = (B, H, N)
+    -> [B, H, N, N]."""
+    _check_rng(rng)
+    if attn_shape is not None:
+        B, H, N = attn_shape
+        m = torch.empty((B, H, N, N), dtype=torch.uint8, device=rng.device)
+        check(lib().vitpe_dropout_mask(SITE_ATTENTION, ptr(rng), ptr(m), 0, B, H, N, float(p), stream_ptr()),
+              "vitpe_dropout_mask")
+        return m
+    m = torch.empty(n, dtype=torch.uint8, device=rng.device)
+    check(lib().vitpe_dropout_mask(SITE_ELEMENT, ptr(rng), ptr(m), n, 0, 0, 0, float(p), stream_ptr()), "vitpe_dropout_mask")
+    return m
+
+
+def dropout_fwd(x, rng, p, resid=None, out=None):
+    """y = [resid +] x . m / (1 - p); the mask is a function of (rng, element index, p) and is not stored."""
+    require_device(x, resid, out)
+    _check_rng(rng)
+    y = out if out is not None else torch.empty_like(x)
+    assert resid is None or (resid.shape == x.shape and resid.dtype == x.dtype)
+    check(lib().vitpe_dropout_fwd(dtype_code(x.dtype), ptr(x), ptr(resid), ptr(y), x.numel(), ptr(rng), float(p),
+                                  stream_ptr()), "vitpe_dropout_fwd")
+    return y
+
+
+def dropout_bwd(dy, rng, p, out=None):
+    require_device(dy, out)
+    _check_rng(rng)
+    dx = out if out is not None else torch.empty_like(dy)
+    check(lib().vitpe_dropout_bwd(dtype_code(dy.dtype), ptr(dy), ptr(dx), dy.numel(), ptr(rng), float(p), stream_ptr()),
+          "vitpe_dropout_bwd")
+    return dx
+
+
+def drop_path_fwd(x, rng, p, resid=None, out=None):
+    """y = [resid +] x * m_b / (1 - p), one decision per sample (leading dimension)."""
+    require_device(x, resid, out)
+    _check_rng(rng)
+    y = out if out is not None else torch.empty_like(x)
+    assert resid is None or (resid.shape == x.shape and resid.dtype == x.dtype)
+    B = x.shape[0]
+    check(lib().vitpe_drop_path_fwd(dtype_code(x.dtype), ptr(x), ptr(resid), ptr(y), B, x.numel() // max(B, 1), ptr(rng),
+                                    float(p), stream_ptr()), "vitpe_drop_path_fwd")
+    return y
+
+
+def drop_path_bwd(dy, rng, p, out=None):
+    require_device(dy, out)
+    _check_rng(rng)
+    dx = out if out is not None else torch.empty_like(dy)
+    B = dy.shape[0]
+    check(lib().vitpe_drop_path_bwd(dtype_code(dy.dtype), ptr(dy), ptr(dx), B, dy.numel() // max(B, 1), ptr(rng), float(p),
+                                    stream_ptr()), "vitpe_drop_path_bwd")
+    return dx
+
+
+def attention_core_fwd_drop(qkv, num_heads, pe: PETables, rng, p, out=None):
+    """attention_core_fwd with attention-probability dropout (softmax -> dropout -> @ v) inside the kernel."""
+    require_device(qkv, out)
+    _check_rng(rng)
+    B, N, D3 = qkv.shape
+    D = D3 // 3
+    HD = D // num_heads
+    o = out if out is not None else torch.empty((B, N, D), dtype=qkv.dtype, device=qkv.device)
+    check(lib().vitpe_attention_core_fwd_drop(dtype_code(qkv.dtype), ptr(qkv), ptr(o), B, N, num_heads, HD, pe.code,
+                                              ptr(pe.cos), ptr(pe.sin), ptr(pe.table), ptr(pe.coeff), pe.grid, pe.degree,
+                                              int(pe.coeff_per_head), ptr(rng), float(p), stream_ptr()),
+          "vitpe_attention_core_fwd_drop")
+    return o
+
+
+def attention_core_bwd_drop(qkv, dout, num_heads, pe: PETables, rng, p, dtable=None, dcoeff=None, dfreqs=None, out=None):
+    """attention_core_bwd of attention_core_fwd_drop: the mask is regenerated from the same rng pair."""
+    require_device(qkv, dout, dtable, dcoeff, dfreqs, out)
+    _check_rng(rng)
+    B, N, D3 = qkv.shape
+    HD = D3 // 3 // num_heads
+    dqkv = out if out is not None else torch.empty_like(qkv)
+    check(lib().vitpe_attention_core_bwd_drop(dtype_code(qkv.dtype), ptr(qkv), ptr(dout), ptr(dqkv), B, N, num_heads, HD,
+                                              pe.code, ptr(pe.cos), ptr(pe.sin), ptr(pe.table), ptr(pe.coeff), pe.grid,
+                                              pe.degree, int(pe.coeff_per_head), ptr(dtable), ptr(dcoeff), ptr(dfreqs),
+                                              ptr(rng), float(p), stream_ptr()), "vitpe_attention_core_bwd_drop")
+    return dqkv
+
+
 # ---- patch embed ----------------------------------------------------------------------------
 def unfold(images, patch, dtype, out=None):
     require_device(images, out)

@@ -177,14 +177,117 @@ def _attn_backward(ctx, dy, _da, _dqkv):
 attention.register_autograd(_attn_backward, setup_context=_attn_setup)
 
 
+# ---- attention with a qkv bias and / or dropout (reference vit.py:28-38: qkv_bias, attn_drop, proj_drop) -------------------
+@torch.library.custom_op("vitpe::attention_drop", mutates_args=())
+def attention_drop(xn: Tensor, wqkv: Tensor, bqkv: Optional[Tensor], wproj: Tensor, bproj: Tensor, resid: Optional[Tensor],
+                   num_heads: int, mode: int, grid: int, pe_param: Optional[Tensor], inv_freq: Optional[Tensor], degree: int,
+                   per_head: bool, cos: Optional[Tensor], sin: Optional[Tensor], tables_grad: bool, attn_p: float,
+                   proj_p: float, rng: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (y, a, qkv): vitpe::attention on the qkv Linear (bias epilogue, the real bias) + attention core route at every
+    geometry -- the one-kernel fused paths have no bias input and no dropout.  attn_p > 0: the dropout core (softmax ->
+    dropout -> @ v inside the kernel); proj_p > 0: the elementwise dropout kernel behind the proj Linear, residual fused.
+    rng: [2, 2] int64 device tensor, the (seed, offset) pairs of the attention-probability site (row 0) and the proj site
+    (row 1); the backward regenerates both masks from it.  tables_grad together with attn_p > 0 is refused."""
+    dt = xn.dtype
+    B, N, D = xn.shape
+    t = _pe_tables(mode, grid, pe_param, inv_freq, degree, per_head, cos, sin)
+    if tables_grad and attn_p > 0.0:
+        raise NotImplementedError("vitpe::attention_drop: gradients of caller rotary tables together with attn_drop > 0")
+    if tables_grad and (cos is None or MODES[mode] not in ("rope-axial", "rope-mixed")):
+        raise L.VitpeError("vitpe::attention_drop: tables_grad needs caller (cos, sin) tables in a rope mode")
+    if (attn_p > 0.0 or proj_p > 0.0) and (rng is None or tuple(rng.shape) != (2, 2)):
+        raise L.VitpeError("vitpe::attention_drop: dropout needs rng, a [2, 2] int64 device tensor")
+    qkv = K.linear(xn.contiguous().view(B * N, D), _shadow(wqkv, dt), bqkv, epi=L.EPI_BIAS).view(B, N, 3 * D)
+    if attn_p > 0.0:
+        a = K.attention_core_fwd_drop(qkv, num_heads, t, rng[0], attn_p)
+    else:
+        a = K.attention_core_fwd(qkv, num_heads, t)
+    r2 = None if resid is None else resid.contiguous().view(B * N, D)
+    if proj_p > 0.0:
+        y = K.linear(a.view(B * N, D), _shadow(wproj, dt), bproj, epi=L.EPI_BIAS)
+        y = K.dropout_fwd(y, rng[1], proj_p, resid=r2)
+    elif r2 is None:
+        y = K.linear(a.view(B * N, D), _shadow(wproj, dt), bproj, epi=L.EPI_BIAS)
+    else:
+        y = K.linear(a.view(B * N, D), _shadow(wproj, dt), bproj, epi=L.EPI_BIAS_RESID, resid=r2)
+    return y.view(B, N, D), a, qkv
+
+
+@attention_drop.register_fake
+def _(xn, wqkv, bqkv, wproj, bproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos, sin, tables_grad,
+      attn_p, proj_p, rng):
+    B, N, D = xn.shape
+    return torch.empty_like(xn), torch.empty_like(xn), xn.new_empty((B, N, 3 * D))
+
+
+def _attn_drop_setup(ctx, inputs, output):
+    (xn, wqkv, bqkv, wproj, bproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos, sin, tables_grad,
+     attn_p, proj_p, rng) = inputs
+    _, a, qkv = output
+    ctx.save_for_backward(xn, wqkv, wproj, a, qkv, pe_param, inv_freq, cos, sin, rng)
+    ctx.meta = (num_heads, mode, grid, degree, per_head, resid is not None, tables_grad, bqkv is not None, attn_p, proj_p)
+
+
+def _attn_drop_backward(ctx, dy, _da, _dqkv):
+    xn, wqkv, wproj, a, qkv, pe_param, inv_freq, cos, sin, rng = ctx.saved_tensors
+    num_heads, mode, grid, degree, per_head, has_resid, tables_grad, has_bqkv, attn_p, proj_p = ctx.meta
+    dt = xn.dtype
+    B, N, D = xn.shape
+    dy2 = dy.contiguous().view(B * N, D)
+    if proj_p > 0.0:   # d(proj output) = dy . m / (1 - p), the proj site's mask regenerated; the residual takes dy itself
+        dy2 = K.dropout_bwd(dy2, rng[1], proj_p)
+    da = K.linear(dy2, _shadow_t(wproj, dt), None, epi=L.EPI_BIAS)
+    dwproj = torch.zeros_like(wproj)
+    dbproj = torch.zeros(D, dtype=torch.float32, device=dy.device)
+    K.gemm_tn(dy2, a.view(B * N, D), dwproj, dbproj)
+    t = _pe_tables(mode, grid, pe_param, inv_freq, degree, per_head, cos, sin)
+    dpe = torch.zeros_like(pe_param) if pe_param is not None else None
+    name = MODES[mode]
+    pe_grads = dict(dtable=dpe if name == "relative" else None, dcoeff=dpe if name == "polynomial" else None,
+                    dfreqs=dpe if name == "rope-mixed" else None)
+    if cos is not None and name == "rope-mixed":   # caller-supplied tables are constants: the frequency gradient is discarded
+        pe_grads["dfreqs"] = torch.zeros(2, num_heads, D // num_heads // 2, dtype=torch.float32, device=xn.device)
+        dpe = None
+    dcos = dsin = None
+    if attn_p > 0.0:
+        dqkv = K.attention_core_bwd_drop(qkv, da.view(B, N, D), num_heads, t, rng[0], attn_p, **pe_grads)
+    elif tables_grad:
+        dcos, dsin = torch.zeros_like(t.cos), torch.zeros_like(t.sin)
+        dqkv = K.attention_core_bwd(qkv, da.view(B, N, D), num_heads, t, dcos=dcos, dsin=dsin)
+        dcos, dsin = dcos.view(cos.shape).to(cos.dtype), dsin.view(sin.shape).to(sin.dtype)
+    else:
+        dqkv = K.attention_core_bwd(qkv, da.view(B, N, D), num_heads, t, **pe_grads)
+    dq2 = dqkv.view(B * N, 3 * D)
+    dxn = K.linear(dq2, _shadow_t(wqkv, dt), None, epi=L.EPI_BIAS).view(B, N, D)
+    dwqkv = torch.zeros_like(wqkv)
+    dbqkv = torch.zeros(3 * D, dtype=torch.float32, device=dy.device) if has_bqkv else None   # gemm_tn's dbias: colsum(dqkv)
+    K.gemm_tn(dq2, xn.contiguous().view(B * N, D), dwqkv, dbqkv)
+    return (dxn, dwqkv, dbqkv, dwproj, dbproj, dy if has_resid else None, None, None, None, dpe, None, None, None, dcos, dsin,
+            None, None, None, None)
+
+
+attention_drop.register_autograd(_attn_drop_backward, setup_context=_attn_drop_setup)
+
+
 # ---- mlp: y = [resid +] fc2(gelu(fc1(xn)))  (timm Mlp, reference vit.py:118,124) ----------------
 @torch.library.custom_op("vitpe::mlp", mutates_args=())
-def mlp(xn: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, resid: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor]:
+def mlp(xn: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, resid: Optional[Tensor], p: float = 0.0,
+        rng: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """p > 0 (timm Mlp's drop, drop1 behind the activation and drop2 behind fc2): fc1 + GELU -> dropout -> fc2 + bias ->
+    dropout [+ resid]; rng [2, 2] int64: the pairs of drop1 (row 0) and drop2 (row 1).  The returned h is then the
+    dropped activation (what fc2 read)."""
     dt = xn.dtype
     shp = xn.shape
     D = shp[-1]
     x2 = xn.contiguous().view(-1, D)
     h, u = K.linear(x2, _shadow(w1, dt), b1, epi=L.EPI_BIAS_GELU)
+    if p > 0.0:
+        if rng is None or tuple(rng.shape) != (2, 2):
+            raise L.VitpeError("vitpe::mlp: dropout needs rng, a [2, 2] int64 device tensor")
+        h = K.dropout_fwd(h, rng[0], p)
+        y = K.linear(h, _shadow(w2, dt), b2, epi=L.EPI_BIAS)
+        y = K.dropout_fwd(y, rng[1], p, resid=None if resid is None else resid.contiguous().view(-1, D))
+        return y.view(shp), h, u
     if resid is None:
         y = K.linear(h, _shadow(w2, dt), b2, epi=L.EPI_BIAS)
     else:
@@ -193,34 +296,86 @@ def mlp(xn: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, resid: Optio
 
 
 @mlp.register_fake
-def _(xn, w1, b1, w2, b2, resid):
+def _(xn, w1, b1, w2, b2, resid, p=0.0, rng=None):
     m = xn.numel() // xn.shape[-1]
     return torch.empty_like(xn), xn.new_empty(m, w1.shape[0]), xn.new_empty(m, w1.shape[0])
 
 
 def _mlp_setup(ctx, inputs, output):
-    xn, w1, b1, w2, b2, resid = inputs
+    xn, w1, b1, w2, b2, resid, p, rng = inputs
     _, h, u = output
-    ctx.save_for_backward(xn, w1, w2, h, u)
+    ctx.save_for_backward(xn, w1, w2, h, u, rng)
     ctx.has_resid = resid is not None
+    ctx.p = p
 
 
 def _mlp_backward(ctx, dy, _dh, _du):
-    xn, w1, w2, h, u = ctx.saved_tensors
+    xn, w1, w2, h, u, rng = ctx.saved_tensors
     dt = xn.dtype
     D = xn.shape[-1]
+    dres = dy if ctx.has_resid else None
     dy2 = dy.contiguous().view(-1, D)
     x2 = xn.contiguous().view(-1, D)
+    if ctx.p > 0.0:
+        dy2 = K.dropout_bwd(dy2, rng[1], ctx.p)
     du = K.linear(dy2, _shadow_t(w2, dt), None, epi=L.EPI_GELU_BWD, u=u)
+    if ctx.p > 0.0:   # (dy W2) . m1 / (1-p) . gelu'(u): the two elementwise factors commute
+        du = K.dropout_bwd(du, rng[0], ctx.p)
     dw2, db2 = torch.zeros_like(w2), torch.zeros(w2.shape[0], dtype=torch.float32, device=dy.device)
     K.gemm_tn(dy2, h, dw2, db2)
     dxn = K.linear(du, _shadow_t(w1, dt), None, epi=L.EPI_BIAS).view(xn.shape)
     dw1, db1 = torch.zeros_like(w1), torch.zeros(w1.shape[0], dtype=torch.float32, device=dy.device)
     K.gemm_tn(du, x2, dw1, db1)
-    return dxn, dw1, db1, dw2, db2, (dy if ctx.has_resid else None)
+    return dxn, dw1, db1, dw2, db2, dres, None, None
 
 
 mlp.register_autograd(_mlp_backward, setup_context=_mlp_setup)
+
+
+# ---- dropout / drop_path: y = [resid +] x . mask / (1 - p) ------------------------------------------
+# (torch.nn.Dropout and timm's DropPath(scale_by_keep=True) -- the latter third-party, parity unpinned -- on the
+#  project's own Philox stream; rng: int64 [2] device tensor (seed, offset), saved for the backward, which regenerates the
+#  mask)
+@torch.library.custom_op("vitpe::dropout", mutates_args=())
+def dropout(x: Tensor, resid: Optional[Tensor], p: float, rng: Tensor) -> Tensor:
+    return K.dropout_fwd(x.contiguous(), rng, p, resid=None if resid is None else resid.contiguous())
+
+
+@dropout.register_fake
+def _(x, resid, p, rng):
+    return torch.empty_like(x)
+
+
+def _drop_setup(ctx, inputs, output):
+    x, resid, p, rng = inputs
+    ctx.save_for_backward(rng)
+    ctx.p, ctx.has_resid = p, resid is not None
+
+
+def _dropout_backward(ctx, dy):
+    (rng,) = ctx.saved_tensors
+    return K.dropout_bwd(dy.contiguous(), rng, ctx.p), (dy if ctx.has_resid else None), None, None
+
+
+dropout.register_autograd(_dropout_backward, setup_context=_drop_setup)
+
+
+@torch.library.custom_op("vitpe::drop_path", mutates_args=())
+def drop_path(x: Tensor, resid: Optional[Tensor], p: float, rng: Tensor) -> Tensor:
+    return K.drop_path_fwd(x.contiguous(), rng, p, resid=None if resid is None else resid.contiguous())
+
+
+@drop_path.register_fake
+def _(x, resid, p, rng):
+    return torch.empty_like(x)
+
+
+def _drop_path_backward(ctx, dy):
+    (rng,) = ctx.saved_tensors
+    return K.drop_path_bwd(dy.contiguous(), rng, ctx.p), (dy if ctx.has_resid else None), None, None
+
+
+drop_path.register_autograd(_drop_path_backward, setup_context=_drop_setup)
 
 
 # ---- patch_embed: images -> tokens (unfold + GEMM + cls + APE), reference vit.py:245-258 ---------

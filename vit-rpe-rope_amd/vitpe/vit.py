@@ -12,12 +12,19 @@ import math
 import torch
 import torch.nn as nn
 
+from . import kernels as K
 from . import ops  # noqa: F401  (registers torch.ops.vitpe.*)
 from ._lib import VitpeError, require_device
 from .positional_encoding import (AbsolutePositionalEncoding, NoPositionalEncoding, PolynomialRPE,
                                   RelativePositionalEncoding, RoPEAxial, RoPEMixed, _MixedTables)
 
 _MODE = {"none": 0, "absolute": 1, "relative": 2, "polynomial": 3, "rope-axial": 4, "rope-mixed": 5}
+
+
+def _check_rate(name, p):
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError(f"vitpe: {name} must be in [0, 1), got {p}")
+    return float(p)
 
 
 def _pe_args(pe, use_rope_tables: bool):
@@ -35,30 +42,47 @@ def _pe_args(pe, use_rope_tables: bool):
 
 class Mlp(nn.Module):
     """fc1 -> GELU(erf) -> fc2, the arithmetic of timm's Mlp as the reference instantiates it
-    (vit.py:118; third-party, parity unpinned).  Same state_dict keys (fc1.*, fc2.*)."""
+    (vit.py:118; third-party, parity unpinned).  Same state_dict keys (fc1.*, fc2.*).  drop > 0 in training: fc1 -> GELU ->
+    dropout -> fc2 -> dropout (timm's drop1 / drop2 order) on the dropout kernels; `last_rng` ([2, 2] int64 device tensor)
+    then holds the (seed, offset) pairs the last forward drew for drop1 (row 0) and drop2 (row 1), None if it drew none."""
 
     def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.):
         super().__init__()
-        if act_layer is not nn.GELU or drop != 0.:
-            raise NotImplementedError("vitpe Mlp: only act_layer=nn.GELU, drop=0 (the reference's configuration)")
+        if act_layer is not nn.GELU:
+            raise NotImplementedError("vitpe Mlp: only act_layer=nn.GELU (the reference's configuration)")
         out_features = out_features or in_features
         hidden_features = hidden_features or in_features
         self.fc1 = nn.Linear(in_features, hidden_features)
         self.act = act_layer()
         self.fc2 = nn.Linear(hidden_features, out_features)
+        self.drop = _check_rate("drop", drop)
+        self.last_rng = None
 
     def forward(self, x, resid=None):
         require_device(x)
+        if self.training and self.drop > 0.:
+            self.last_rng = K.new_rng_pairs(2, x.device)
+            return torch.ops.vitpe.mlp(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, resid,
+                                       self.drop, self.last_rng)[0]
+        self.last_rng = None   # (no pairs drawn by this forward)
         return torch.ops.vitpe.mlp(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, resid)[0]
 
 
 class Attention(nn.Module):
-    """reference vit.py:14-98; forward(x, freqs_cis=None) returns proj(attention(x))."""
+    """reference vit.py:14-98; forward(x, freqs_cis=None) returns proj(attention(x)).
+
+    qkv_bias, or a non-zero attn_drop / proj_drop in training, takes the qkv Linear (bias epilogue) + attention core route
+    (the one-kernel fused paths have neither a bias input nor dropout); attn_drop runs inside the core kernel, proj_drop
+    as the elementwise dropout kernel.  In eval mode, or with zero rates, the dropout kernels are not launched.  `last_rng`
+    ([2, 2] int64 device tensor) holds the (seed, offset) pairs the last forward drew (None if it drew none) for the attention-probability
+    site (row 0) and the proj site (row 1).  The one refused combination: gradients of caller-supplied rotary tables
+    together with attn_drop > 0 (NotImplementedError)."""
 
     def __init__(self, dim, num_heads=8, qkv_bias=False, attn_drop=0., proj_drop=0.):
         super().__init__()
-        if qkv_bias or attn_drop != 0. or proj_drop != 0.:
-            raise NotImplementedError("vitpe Attention: qkv_bias=False and zero dropout only (as the reference builds it)")
+        self.attn_drop_p = _check_rate("attn_drop", attn_drop)
+        self.proj_drop_p = _check_rate("proj_drop", proj_drop)
+        self.last_rng = None
         self.num_heads = num_heads
         self.head_dim = dim // num_heads
         self.scale = self.head_dim ** -0.5
@@ -97,8 +121,22 @@ class Attention(nn.Module):
                 # qkv Linear + core route, whose backward returns d cos / d sin (vitpe::attention, tables_grad)
                 tables_grad = torch.is_grad_enabled() and (cos.requires_grad or sin.requires_grad)
                 mode, pe_param, inv_freq = (_MODE["rope-axial"] if cos.dim() == 2 else _MODE["rope-mixed"]), None, None
-        y, _, _ = torch.ops.vitpe.attention(x, self.qkv.weight, self.proj.weight, self.proj.bias, resid, self.num_heads,
-                                         mode, grid, pe_param, inv_freq, degree, per_head, cos, sin, tables_grad)
+        attn_p = self.attn_drop_p if self.training else 0.
+        proj_p = self.proj_drop_p if self.training else 0.
+        self.last_rng = None   # (set below if this forward draws pairs)
+        if self.qkv.bias is None and attn_p == 0. and proj_p == 0.:
+            y, _, _ = torch.ops.vitpe.attention(x, self.qkv.weight, self.proj.weight, self.proj.bias, resid, self.num_heads,
+                                             mode, grid, pe_param, inv_freq, degree, per_head, cos, sin, tables_grad)
+            return y
+        if tables_grad and attn_p > 0.:
+            raise NotImplementedError("vitpe Attention: gradients of caller-supplied rotary tables together with "
+                                      "attn_drop > 0 (pass constant tables, or set attn_drop=0)")
+        rng = None
+        if attn_p > 0. or proj_p > 0.:
+            rng = self.last_rng = K.new_rng_pairs(2, x.device)
+        y, _, _ = torch.ops.vitpe.attention_drop(x, self.qkv.weight, self.qkv.bias, self.proj.weight, self.proj.bias, resid,
+                                              self.num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos, sin,
+                                              tables_grad, attn_p, proj_p, rng)
         return y
 
     def _own_mixed_tables(self, cos, sin):
@@ -122,16 +160,27 @@ class Block(nn.Module):
     def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, drop=0., attn_drop=0.,
                  drop_path=0., act_layer=nn.GELU, norm_layer=nn.LayerNorm):
         super().__init__()
-        if drop_path > 0. or norm_layer is not nn.LayerNorm:
-            raise NotImplementedError("vitpe Block: drop_path=0 and nn.LayerNorm only (as the reference builds it)")
+        if norm_layer is not nn.LayerNorm:
+            raise NotImplementedError("vitpe Block: nn.LayerNorm only (as the reference builds it)")
         self.norm1 = norm_layer(dim)
         self.attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop)
+        # stochastic depth (reference vit.py:115: timm DropPath, scale_by_keep=True -- third-party, parity unpinned): one
+        # keep decision per sample for each branch, on the drop-path kernel with the residual fused.  No parameters, so
+        # nn.Identity keeps the reference's attribute and state_dict surface; the rate lives in drop_path_p.
         self.drop_path = nn.Identity()
+        self.drop_path_p = _check_rate("drop_path", drop_path)
+        self.last_rng = None   # [2, 2] int64: the pairs of the attention branch (row 0) and the MLP branch (row 1)
         self.norm2 = norm_layer(dim)
         self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
 
     def forward(self, x, freqs_cis=None):
         n1 = torch.ops.vitpe.layer_norm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)[0]
+        if self.training and self.drop_path_p > 0.:
+            rng = self.last_rng = K.new_rng_pairs(2, x.device)
+            x = torch.ops.vitpe.drop_path(self.attn(n1, freqs_cis=freqs_cis), x, self.drop_path_p, rng[0])
+            n2 = torch.ops.vitpe.layer_norm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps)[0]
+            return torch.ops.vitpe.drop_path(self.mlp(n2), x, self.drop_path_p, rng[1])
+        self.last_rng = None   # (no pairs drawn by this forward)
         x = self.attn(n1, freqs_cis=freqs_cis, resid=x)      # x + attn(norm1(x)), residual fused in the proj GEMM
         n2 = torch.ops.vitpe.layer_norm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps)[0]
         return self.mlp(n2, resid=x)                          # x + mlp(norm2(x)), residual fused in the fc2 GEMM
@@ -141,13 +190,20 @@ class Block(nn.Module):
 
 
 class VisionTransformer(nn.Module):
-    """reference vit.py:131-285, constructor kept verbatim (vit.py:148-151)."""
+    """reference vit.py:131-285, constructor kept verbatim (vit.py:148-151); keyword-only extras behind it: qkv_bias,
+    drop_rate (proj and Mlp dropout), attn_drop_rate, drop_path_rate (stochastic depth, rising linearly from 0 at the first
+    block to drop_path_rate at the last) -- what the reference's Block accepts but its VisionTransformer never passes."""
 
     def __init__(self, img_size=32, patch_size=4, in_chans=3, num_classes=10,
                  embed_dim=192, depth=6, num_heads=6, mlp_ratio=4.,
                  pos_encoding='absolute', rope_theta=100.0,
-                 poly_degree=3, poly_shared_heads=True):
+                 poly_degree=3, poly_shared_heads=True, *,
+                 qkv_bias=False, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.):
         super().__init__()
+        self.qkv_bias = bool(qkv_bias)
+        self.drop_rate = _check_rate("drop_rate", drop_rate)
+        self.attn_drop_rate = _check_rate("attn_drop_rate", attn_drop_rate)
+        self.drop_path_rate = _check_rate("drop_path_rate", drop_path_rate)
         self.num_classes = num_classes
         self.embed_dim = embed_dim
         self.patch_size = patch_size
@@ -182,7 +238,9 @@ class VisionTransformer(nn.Module):
         else:
             raise ValueError(f"Unknown positional encoding type: {pos_encoding}")
 
-        self.blocks = nn.ModuleList([Block(embed_dim, num_heads, mlp_ratio) for _ in range(depth)])
+        dpr = [self.drop_path_rate * i / max(depth - 1, 1) for i in range(depth)]
+        self.blocks = nn.ModuleList([Block(embed_dim, num_heads, mlp_ratio, qkv_bias=self.qkv_bias, drop=self.drop_rate,
+                                           attn_drop=self.attn_drop_rate, drop_path=dpr[i]) for i in range(depth)])
         if not self.use_pos_embed_in_forward:
             for block in self.blocks:  # ONE shared PE module, registered in every block (vit.py:205-207)
                 block.set_pos_encoding(self.pos_embed)
