@@ -1379,28 +1379,39 @@ extern "C" int vitpe_fused_attention_supported(int dtype, int N, int D, int HD) 
   return (dtype == 0 || dtype == 1) && HD == 32 && MT == 5 && (D == 192 || D == 96);
 }
 
-static int check_pe(int mode, const float* cos, const float* sin, const float* table, const float* coeff,
-                    int N, int grid, int degree) {
-  if (mode == PE_ROPE_AXIAL || mode == PE_ROPE_MIXED) {
-    if (!cos || !sin || grid * grid != N - 1) return 0;
-  }
-  if (mode == PE_RELATIVE && !table) return 0;
-  if (mode == PE_POLY && (!coeff || degree < 0 || degree > 7 || grid * grid != N - 1)) return 0;
-  return mode >= PE_NONE && mode <= PE_ROPE_MIXED;
+// The four product entry points share one body each way: gamma == NULL is the plain variant (x already layer-normed).
+static int fused_fwd(int dtype, const void* x, const float* gamma, const float* beta, const float* mean,
+                     const float* rstd, void* xn_out, const void* wqkv, void* out, int B, int N, int D, int HD,
+                     const PeArgs& pe, hipStream_t stream) {
+  VITPE_REQUIRE(x && wqkv && out && B >= 0 && N >= 2);
+  VITPE_REQUIRE(pe_ok(pe, N, 0, 0));
+  if (B == 0) return 0;
+  AttnArgs a = attn_args(pe, B, N, 0, HD);
+  a.xn = x; a.wqkv = wqkv; a.out = out;
+  a.ln_gamma = gamma; a.ln_beta = beta; a.ln_mean = mean; a.ln_rstd = rstd; a.xn_out = xn_out;
+  return dispatch_attn(false, dtype, D, HD, a, stream);
+}
+
+static int fused_bwd(int dtype, const void* x, const float* gamma, const float* beta, const float* mean,
+                     const float* rstd, const void* wqkv, const void* dout, void* dqkv, int B, int N, int D, int HD,
+                     const PeArgs& pe, float* dtable, float* dcoeff, float* dfreqs, hipStream_t stream) {
+  VITPE_REQUIRE(x && wqkv && dout && dqkv && B >= 0 && N >= 2);
+  VITPE_REQUIRE(pe_ok(pe, N, 0, 0));
+  VITPE_REQUIRE(pe_grads_ok(pe.mode, dtable, dcoeff, dfreqs));
+  if (B == 0) return 0;
+  AttnArgs a = attn_args(pe, B, N, 0, HD);
+  a.xn = x; a.wqkv = wqkv; a.out = dqkv; a.dout = dout;
+  a.dtable = dtable; a.dcoeff = dcoeff; a.dfreqs = dfreqs;
+  a.ln_gamma = gamma; a.ln_beta = beta; a.ln_mean = mean; a.ln_rstd = rstd;
+  return dispatch_attn(true, dtype, D, HD, a, stream);
 }
 
 extern "C" int vitpe_fused_attention_fwd(int dtype, const void* xn, const void* wqkv, void* out, int B, int N,
                                          int D, int HD, int mode, const float* cos, const float* sin,
                                          const float* table, const float* coeff, int grid, int degree,
                                          int coeff_per_head, hipStream_t stream) {
-  VITPE_REQUIRE(xn && wqkv && out && B >= 0 && N >= 2);
-  VITPE_REQUIRE(check_pe(mode, cos, sin, table, coeff, N, grid, degree));
-  if (B == 0) return 0;
-  AttnArgs a{};
-  a.xn = xn; a.wqkv = wqkv; a.out = out; a.cos = cos; a.sin = sin; a.table = table; a.coeff = coeff;
-  a.B = B; a.N = N; a.mode = mode; a.grid = grid; a.degree = degree; a.coeff_per_head = coeff_per_head;
-  a.scale = 1.0f / sqrtf((float)HD);
-  return dispatch_attn(false, dtype, D, HD, a, stream);
+  return fused_fwd(dtype, xn, nullptr, nullptr, nullptr, nullptr, nullptr, wqkv, out, B, N, D, HD,
+                   {mode, cos, sin, table, coeff, grid, degree, coeff_per_head}, stream);
 }
 
 // Same as vitpe_fused_attention_fwd with the preceding LayerNorm fused into the token staging:
@@ -1411,15 +1422,9 @@ extern "C" int vitpe_fused_attention_fwd_ln(int dtype, const void* x, const floa
                                             void* out, int B, int N, int D, int HD, int mode, const float* cos,
                                             const float* sin, const float* table, const float* coeff, int grid,
                                             int degree, int coeff_per_head, hipStream_t stream) {
-  VITPE_REQUIRE(x && gamma && beta && mean && rstd && wqkv && out && B >= 0 && N >= 2);
-  VITPE_REQUIRE(check_pe(mode, cos, sin, table, coeff, N, grid, degree));
-  if (B == 0) return 0;
-  AttnArgs a{};
-  a.xn = x; a.wqkv = wqkv; a.out = out; a.cos = cos; a.sin = sin; a.table = table; a.coeff = coeff;
-  a.ln_gamma = gamma; a.ln_beta = beta; a.ln_mean = mean; a.ln_rstd = rstd; a.xn_out = xn_out;
-  a.B = B; a.N = N; a.mode = mode; a.grid = grid; a.degree = degree; a.coeff_per_head = coeff_per_head;
-  a.scale = 1.0f / sqrtf((float)HD);
-  return dispatch_attn(false, dtype, D, HD, a, stream);
+  VITPE_REQUIRE(gamma && beta && mean && rstd);
+  return fused_fwd(dtype, x, gamma, beta, mean, rstd, xn_out, wqkv, out, B, N, D, HD,
+                   {mode, cos, sin, table, coeff, grid, degree, coeff_per_head}, stream);
 }
 
 extern "C" int vitpe_fused_attention_bwd(int dtype, const void* xn, const void* wqkv, const void* dout,
@@ -1427,18 +1432,8 @@ extern "C" int vitpe_fused_attention_bwd(int dtype, const void* xn, const void* 
                                          const float* sin, const float* table, const float* coeff, int grid,
                                          int degree, int coeff_per_head, float* dtable, float* dcoeff,
                                          float* dfreqs, hipStream_t stream) {
-  VITPE_REQUIRE(xn && wqkv && dout && dqkv && B >= 0 && N >= 2);
-  VITPE_REQUIRE(check_pe(mode, cos, sin, table, coeff, N, grid, degree));
-  if (mode == PE_RELATIVE) VITPE_REQUIRE(dtable != nullptr);
-  if (mode == PE_POLY) VITPE_REQUIRE(dcoeff != nullptr);
-  if (mode == PE_ROPE_MIXED) VITPE_REQUIRE(dfreqs != nullptr);
-  if (B == 0) return 0;
-  AttnArgs a{};
-  a.xn = xn; a.wqkv = wqkv; a.out = dqkv; a.dout = dout; a.cos = cos; a.sin = sin; a.table = table;
-  a.coeff = coeff; a.dtable = dtable; a.dcoeff = dcoeff; a.dfreqs = dfreqs;
-  a.B = B; a.N = N; a.mode = mode; a.grid = grid; a.degree = degree; a.coeff_per_head = coeff_per_head;
-  a.scale = 1.0f / sqrtf((float)HD);
-  return dispatch_attn(true, dtype, D, HD, a, stream);
+  return fused_bwd(dtype, xn, nullptr, nullptr, nullptr, nullptr, wqkv, dout, dqkv, B, N, D, HD,
+                   {mode, cos, sin, table, coeff, grid, degree, coeff_per_head}, dtable, dcoeff, dfreqs, stream);
 }
 
 // vitpe_fused_attention_bwd with the LayerNorm recomputed while staging (x = RAW tokens + their row statistics): the
@@ -1449,19 +1444,9 @@ extern "C" int vitpe_fused_attention_bwd_ln(int dtype, const void* x, const floa
                                             const float* sin, const float* table, const float* coeff, int grid,
                                             int degree, int coeff_per_head, float* dtable, float* dcoeff,
                                             float* dfreqs, hipStream_t stream) {
-  VITPE_REQUIRE(x && gamma && beta && mean && rstd && wqkv && dout && dqkv && B >= 0 && N >= 2);
-  VITPE_REQUIRE(check_pe(mode, cos, sin, table, coeff, N, grid, degree));
-  if (mode == PE_RELATIVE) VITPE_REQUIRE(dtable != nullptr);
-  if (mode == PE_POLY) VITPE_REQUIRE(dcoeff != nullptr);
-  if (mode == PE_ROPE_MIXED) VITPE_REQUIRE(dfreqs != nullptr);
-  if (B == 0) return 0;
-  AttnArgs a{};
-  a.xn = x; a.wqkv = wqkv; a.out = dqkv; a.dout = dout; a.cos = cos; a.sin = sin; a.table = table;
-  a.coeff = coeff; a.dtable = dtable; a.dcoeff = dcoeff; a.dfreqs = dfreqs;
-  a.ln_gamma = gamma; a.ln_beta = beta; a.ln_mean = mean; a.ln_rstd = rstd;
-  a.B = B; a.N = N; a.mode = mode; a.grid = grid; a.degree = degree; a.coeff_per_head = coeff_per_head;
-  a.scale = 1.0f / sqrtf((float)HD);
-  return dispatch_attn(true, dtype, D, HD, a, stream);
+  VITPE_REQUIRE(gamma && beta && mean && rstd);
+  return fused_bwd(dtype, x, gamma, beta, mean, rstd, wqkv, dout, dqkv, B, N, D, HD,
+                   {mode, cos, sin, table, coeff, grid, degree, coeff_per_head}, dtable, dcoeff, dfreqs, stream);
 }
 
 // debug: bf16 d=192 rope-axial forward with phase stamps: census[(wg * 16 + wave) * 8 + slot], slots 0 start,
@@ -1469,9 +1454,8 @@ extern "C" int vitpe_fused_attention_bwd_ln(int dtype, const void* x, const floa
 extern "C" int vitpe_debug_attn_census(const void* xn, const void* wqkv, void* out, const float* cos, const float* sin,
                                        int B, unsigned long long* census, hipStream_t stream) {
   VITPE_REQUIRE(xn && wqkv && out && cos && sin && census && B > 0);
-  AttnArgs a{};
-  a.xn = xn; a.wqkv = wqkv; a.out = out; a.cos = cos; a.sin = sin; a.B = B; a.N = 65; a.mode = PE_ROPE_AXIAL; a.grid = 8;
-  a.scale = 0.17677669f; a.census = census;
+  AttnArgs a = attn_args({PE_ROPE_AXIAL, cos, sin, nullptr, nullptr, 8, 0, 0}, B, 65, 0, 32);
+  a.xn = xn; a.wqkv = wqkv; a.out = out; a.census = census;
   hipLaunchKernelGGL((attn_fwd_kernel<bf16, 32, 192, 5, KM_ROPE, 65, 2, false, true>), dim3((B + 1) / 2), dim3(768), 0, stream, a);
   VITPE_CHECK_LAUNCH();
 }

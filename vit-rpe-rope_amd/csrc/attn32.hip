@@ -670,16 +670,12 @@ extern "C" int vitpe_fused_attention_fwd_wide(int dtype, const void* x, const fl
   VITPE_REQUIRE(x && wqkv_wide && out && B >= 0);
   if (!vitpe_fused_attention_wide_supported(dtype, N, D, HD)) return (int)hipErrorNotSupported;
   if (gamma != nullptr) VITPE_REQUIRE(beta && mean && rstd);
-  if (mode == PE_ROPE_AXIAL || mode == PE_ROPE_MIXED) VITPE_REQUIRE(cos && sin && grid * grid == N - 1);
-  if (mode == PE_RELATIVE) VITPE_REQUIRE(table != nullptr);
-  if (mode == PE_POLY) VITPE_REQUIRE(coeff && degree >= 0 && degree <= 7 && grid * grid == N - 1);
-  VITPE_REQUIRE(mode >= PE_NONE && mode <= PE_ROPE_MIXED);
+  const PeArgs pe{mode, cos, sin, table, coeff, grid, degree, coeff_per_head};
+  VITPE_REQUIRE(pe_ok(pe, N, 0, 0));
   if (B == 0) return 0;
-  AttnArgs a{};
-  a.xn = x; a.wqkv = wqkv_wide; a.out = out; a.cos = cos; a.sin = sin; a.table = table; a.coeff = coeff;
+  AttnArgs a = attn_args(pe, B, N, 0, HD);
+  a.xn = x; a.wqkv = wqkv_wide; a.out = out;
   a.ln_gamma = gamma; a.ln_beta = beta; a.ln_mean = mean; a.ln_rstd = rstd; a.xn_out = gamma ? xn_out : nullptr;
-  a.B = B; a.N = N; a.mode = mode; a.grid = grid; a.degree = degree; a.coeff_per_head = coeff_per_head;
-  a.scale = 1.0f / sqrtf((float)HD);
   switch (mode) {
     case PE_RELATIVE: return launch_wide<KM_RELATIVE>(a, stream);
     case PE_POLY: return launch_wide<KM_POLY>(a, stream);
@@ -695,9 +691,8 @@ extern "C" int vitpe_fused_attention_fwd_wide(int dtype, const void* x, const fl
 extern "C" int vitpe_debug_attn32_census(const void* xn, const void* wqkv_wide, void* out, const float* cos,
                                          const float* sin, int B, unsigned long long* census, int exp, hipStream_t stream) {
   VITPE_REQUIRE(xn && wqkv_wide && out && cos && sin && census && B > 0);
-  AttnArgs a{};
-  a.xn = xn; a.wqkv = wqkv_wide; a.out = out; a.cos = cos; a.sin = sin; a.B = B; a.N = 65; a.mode = PE_ROPE_AXIAL; a.grid = 8;
-  a.scale = 0.17677669f; a.census = census;
+  AttnArgs a = attn_args({PE_ROPE_AXIAL, cos, sin, nullptr, nullptr, 8, 0, 0}, B, 65, 0, 32);
+  a.xn = xn; a.wqkv = wqkv_wide; a.out = out; a.census = census;
   const dim3 grid((B + 1) / 2), block(768);
   if (exp == 1) hipLaunchKernelGGL((attn32_fwd_kernel<KM_ROPE, false, false, true, 1>), grid, block, 0, stream, a);
   else if (exp == 2) hipLaunchKernelGGL((attn32_fwd_kernel<KM_ROPE, false, false, true, 2>), grid, block, 0, stream, a);

@@ -41,6 +41,45 @@ struct AttnArgs {
   float drop_rs;
 };
 
+// ---- host side: the one argument path behind every attention entry point (attn.hip, attn32.hip, attn_core.hip) ----
+// The positional-encoding operands of the C ABI, in its order.
+struct PeArgs {
+  int mode;
+  const float *cos, *sin, *table, *coeff;
+  int grid, degree, coeff_per_head;
+};
+
+// The operands the mode needs are there and fit N tokens.  hmax: head bound of rope-mixed (the core's frequency-gradient
+// scratch, CORE_HMAX), 0 = none.
+inline bool pe_ok(const PeArgs& pe, int N, int H, int hmax) {
+  if (pe.mode == PE_ROPE_AXIAL || pe.mode == PE_ROPE_MIXED) {
+    if (!pe.cos || !pe.sin || pe.grid * pe.grid != N - 1) return false;
+    if (pe.mode == PE_ROPE_MIXED && hmax && H > hmax) return false;
+  }
+  if (pe.mode == PE_RELATIVE && !pe.table) return false;
+  if (pe.mode == PE_POLY && (!pe.coeff || pe.degree < 0 || pe.degree > 7 || pe.grid * pe.grid != N - 1)) return false;
+  return pe.mode >= PE_NONE && pe.mode <= PE_ROPE_MIXED;
+}
+
+// A backward pass accumulates into the gradient buffer of its mode's parameters.
+inline bool pe_grads_ok(int mode, const float* dtable, const float* dcoeff, const float* dfreqs) {
+  if (mode == PE_RELATIVE) return dtable != nullptr;
+  if (mode == PE_POLY) return dcoeff != nullptr;
+  if (mode == PE_ROPE_MIXED) return dfreqs != nullptr;
+  return true;
+}
+
+// Zeroed kernel arguments with the PE operands, the shape and the logit scale set; the entry points add their tensors.
+// (H: read by the attention core only -- the fused kernels have it as a template parameter.)
+inline AttnArgs attn_args(const PeArgs& pe, int B, int N, int H, int HD) {
+  AttnArgs a{};
+  a.cos = pe.cos; a.sin = pe.sin; a.table = pe.table; a.coeff = pe.coeff;
+  a.mode = pe.mode; a.grid = pe.grid; a.degree = pe.degree; a.coeff_per_head = pe.coeff_per_head;
+  a.B = B; a.N = N; a.H = H;
+  a.scale = 1.0f / sqrtf((float)HD);
+  return a;
+}
+
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float LN2 = 0.6931471805599453f;
 

@@ -796,7 +796,10 @@ constexpr bool core_fits() {
 }
 #define VITPE_CORE_MTS(X, T, HD) X(T, HD, 2) X(T, HD, 4) X(T, HD, 5) X(T, HD, 10) X(T, HD, 13) X(T, HD, 17)
 
-// (the head dimensions 24 / 48 / 96 / 128 are instantiated in attn_core_hd.hip, one translation unit per head dimension)
+// THE list of head dimensions: X(HD, OWN_TU).  OWN_TU = 1: instantiated in attn_core_hd.hip, one translation unit per head
+// dimension -- csrc/Makefile's CORE_HDS names exactly these, keep the two in step; 0: instantiated in attn_core.hip.
+#define VITPE_CORE_HDS(X) X(64, 0) X(32, 0) X(24, 1) X(48, 1) X(96, 1) X(128, 1)
+
 template <typename T, int HD>
 __attribute__((visibility("hidden"))) int dispatch_core_t(bool bwd, int MT, const AttnArgs& a, hipStream_t s) {
 #define VITPE_CORE_CASE(T_, HD_, MT_)                                                    \
@@ -817,16 +820,25 @@ __attribute__((visibility("hidden"))) bool core_supported_t(int MT) {
   return false;
 }
 
-#define VITPE_CORE_EXTERN_HD(HD)                                                                  \
-  extern template int dispatch_core_t<bf16, HD>(bool, int, const AttnArgs&, hipStream_t);        \
-  extern template int dispatch_core_t<float, HD>(bool, int, const AttnArgs&, hipStream_t);       \
-  extern template bool core_supported_t<bf16, HD>(int);                                          \
-  extern template bool core_supported_t<float, HD>(int);
-#ifndef VITPE_CORE_HD_TU
-VITPE_CORE_EXTERN_HD(24)
-VITPE_CORE_EXTERN_HD(48)
-VITPE_CORE_EXTERN_HD(96)
-VITPE_CORE_EXTERN_HD(128)
+// VITPE_CORE_HD_TU (attn_core_hd.hip): the translation unit instantiates the OWN_TU head dimensions (all of them, or
+// the one VITPE_CORE_HD names); everywhere else they are extern.
+#ifdef VITPE_CORE_HD_TU
+#define VITPE_CORE_HD_LINKAGE
+#else
+#define VITPE_CORE_HD_LINKAGE extern
+#endif
+#define VITPE_CORE_DECLARE_HD(HD)                                                                       \
+  VITPE_CORE_HD_LINKAGE template int dispatch_core_t<bf16, HD>(bool, int, const AttnArgs&, hipStream_t);  \
+  VITPE_CORE_HD_LINKAGE template int dispatch_core_t<float, HD>(bool, int, const AttnArgs&, hipStream_t); \
+  VITPE_CORE_HD_LINKAGE template bool core_supported_t<bf16, HD>(int);                                    \
+  VITPE_CORE_HD_LINKAGE template bool core_supported_t<float, HD>(int);
+#define VITPE_CORE_DECLARE_HD_0(HD)
+#define VITPE_CORE_DECLARE_HD_1(HD) VITPE_CORE_DECLARE_HD(HD)
+#define VITPE_CORE_DECLARE_X(HD, OWN_TU) VITPE_CORE_DECLARE_HD_##OWN_TU(HD)
+#ifdef VITPE_CORE_HD
+VITPE_CORE_DECLARE_HD(VITPE_CORE_HD)
+#else
+VITPE_CORE_HDS(VITPE_CORE_DECLARE_X)
 #endif
 
 }  // namespace vitpe

@@ -274,55 +274,59 @@ using namespace vitpe;
 
 static int dispatch_core(bool bwd, int dtype, int HD, const AttnArgs& a, hipStream_t s) {
   const int MT = (a.N + 15) / 16;
-  if (dtype == 1 && HD == 64) return dispatch_core_t<bf16, 64>(bwd, MT, a, s);
-  if (dtype == 1 && HD == 32) return dispatch_core_t<bf16, 32>(bwd, MT, a, s);
-  if (dtype == 0 && HD == 64) return dispatch_core_t<float, 64>(bwd, MT, a, s);
-  if (dtype == 0 && HD == 32) return dispatch_core_t<float, 32>(bwd, MT, a, s);
-#define VITPE_CORE_HD_CASE(HD_)                                             \
-  if (dtype == 1 && HD == HD_) return dispatch_core_t<bf16, HD_>(bwd, MT, a, s); \
-  if (dtype == 0 && HD == HD_) return dispatch_core_t<float, HD_>(bwd, MT, a, s);
-  VITPE_CORE_HD_CASE(24) VITPE_CORE_HD_CASE(48) VITPE_CORE_HD_CASE(96) VITPE_CORE_HD_CASE(128)
-#undef VITPE_CORE_HD_CASE
+#define VITPE_CORE_BF16_CASE(HD_, OWN_TU_) if (dtype == 1 && HD == HD_) return dispatch_core_t<bf16, HD_>(bwd, MT, a, s);
+#define VITPE_CORE_F32_CASE(HD_, OWN_TU_) if (dtype == 0 && HD == HD_) return dispatch_core_t<float, HD_>(bwd, MT, a, s);
+  VITPE_CORE_HDS(VITPE_CORE_BF16_CASE)
+  VITPE_CORE_HDS(VITPE_CORE_F32_CASE)
+#undef VITPE_CORE_BF16_CASE
+#undef VITPE_CORE_F32_CASE
   return (int)hipErrorNotSupported;
 }
 
 extern "C" int vitpe_attention_core_supported(int dtype, int N, int HD) {
   const int MT = (N + 15) / 16;
   if (N < 2) return 0;
-  if (dtype == 1 && HD == 64) return core_supported_t<bf16, 64>(MT);
-  if (dtype == 1 && HD == 32) return core_supported_t<bf16, 32>(MT);
-  if (dtype == 0 && HD == 64) return core_supported_t<float, 64>(MT);
-  if (dtype == 0 && HD == 32) return core_supported_t<float, 32>(MT);
-#define VITPE_CORE_HD_CASE(HD_)                                   \
-  if (dtype == 1 && HD == HD_) return core_supported_t<bf16, HD_>(MT); \
-  if (dtype == 0 && HD == HD_) return core_supported_t<float, HD_>(MT);
-  VITPE_CORE_HD_CASE(24) VITPE_CORE_HD_CASE(48) VITPE_CORE_HD_CASE(96) VITPE_CORE_HD_CASE(128)
-#undef VITPE_CORE_HD_CASE
+#define VITPE_CORE_BF16_CASE(HD_, OWN_TU_) if (dtype == 1 && HD == HD_) return core_supported_t<bf16, HD_>(MT);
+#define VITPE_CORE_F32_CASE(HD_, OWN_TU_) if (dtype == 0 && HD == HD_) return core_supported_t<float, HD_>(MT);
+  VITPE_CORE_HDS(VITPE_CORE_BF16_CASE)
+  VITPE_CORE_HDS(VITPE_CORE_F32_CASE)
+#undef VITPE_CORE_BF16_CASE
+#undef VITPE_CORE_F32_CASE
   return 0;
 }
 
-static int core_check_pe(int mode, const float* cos, const float* sin, const float* table, const float* coeff, int N,
-                         int H, int grid, int degree) {
-  if (mode == PE_ROPE_AXIAL || mode == PE_ROPE_MIXED) {
-    if (!cos || !sin || grid * grid != N - 1) return 0;
-    if (mode == PE_ROPE_MIXED && H > CORE_HMAX) return 0;
-  }
-  if (mode == PE_RELATIVE && !table) return 0;
-  if (mode == PE_POLY && (!coeff || degree < 0 || degree > 7 || grid * grid != N - 1)) return 0;
-  return mode >= PE_NONE && mode <= PE_ROPE_MIXED;
+// The one body behind the five core entry points.  out: the merged heads (forward) or dqkv (backward).  rng != NULL with
+// p > 0: the dropout kernels; p == 0 launches exactly the kernels without it.  workspace != NULL
+// (vitpe_attention_core_bwd_tables): the backward also returns the gradients w.r.t. the caller's rotary tables, so the mode
+// is a rope mode and dtable / dcoeff / dfreqs are not looked at.
+static int core_entry(bool bwd, int dtype, const void* qkv, const void* dout, void* out, int B, int N, int H, int HD,
+                      const PeArgs& pe, float* dtable, float* dcoeff, float* dfreqs, const unsigned long long* rng, float p,
+                      float* dcos, float* dsin, float* workspace, hipStream_t stream) {
+  const bool tables = workspace != nullptr;
+  VITPE_REQUIRE(qkv && (dout || !bwd) && out && B >= 0 && N >= 2 && H >= 1);
+  if (tables) VITPE_REQUIRE(pe.mode == PE_ROPE_AXIAL || pe.mode == PE_ROPE_MIXED);
+  VITPE_REQUIRE(pe_ok(pe, N, H, CORE_HMAX));
+  if (tables) VITPE_REQUIRE(dcos && dsin);
+  else if (bwd) VITPE_REQUIRE(pe_grads_ok(pe.mode, dtable, dcoeff, dfreqs));
+  if (B == 0) return 0;
+  AttnArgs a = attn_args(pe, B, N, H, HD);
+  a.qkv = qkv; a.dout = dout; a.out = out;
+  if (tables) a.tab_slab = workspace;
+  else if (bwd) { a.dtable = dtable; a.dcoeff = dcoeff; a.dfreqs = dfreqs; }
+  if (rng && p > 0.0f) { a.rng = rng; a.drop_thr = drop_threshold(p); a.drop_rs = drop_scale(p); }
+  const int e = dispatch_core(bwd, dtype, HD, a, stream);
+  if (e || !tables) return e;
+  // every (q/k, image[, head]) wrote its contribution into a slab of the workspace: sum them in a fixed order
+  const bool mixed = pe.mode == PE_ROPE_MIXED;
+  const long long L = (long long)(mixed ? H : 1) * (N - 1) * (HD / 2);
+  return reduce_parts(workspace, mixed ? 2 * B : 2 * B * H, L, dcos, dsin, stream);
 }
 
 extern "C" int vitpe_attention_core_fwd(int dtype, const void* qkv, void* out, int B, int N, int H, int HD, int mode,
                                         const float* cos, const float* sin, const float* table, const float* coeff,
                                         int grid, int degree, int coeff_per_head, hipStream_t stream) {
-  VITPE_REQUIRE(qkv && out && B >= 0 && N >= 2 && H >= 1);
-  VITPE_REQUIRE(core_check_pe(mode, cos, sin, table, coeff, N, H, grid, degree));
-  if (B == 0) return 0;
-  AttnArgs a{};
-  a.qkv = qkv; a.out = out; a.cos = cos; a.sin = sin; a.table = table; a.coeff = coeff;
-  a.B = B; a.N = N; a.H = H; a.mode = mode; a.grid = grid; a.degree = degree; a.coeff_per_head = coeff_per_head;
-  a.scale = 1.0f / sqrtf((float)HD);
-  return dispatch_core(false, dtype, HD, a, stream);
+  return core_entry(false, dtype, qkv, nullptr, out, B, N, H, HD, {mode, cos, sin, table, coeff, grid, degree, coeff_per_head},
+                    nullptr, nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr, nullptr, stream);
 }
 
 // Attention-probability dropout inside the core (reference vit.py:84-88, softmax -> attn_drop -> @ v).  p == 0 launches
@@ -331,16 +335,9 @@ extern "C" int vitpe_attention_core_fwd_drop(int dtype, const void* qkv, void* o
                                              const float* cos, const float* sin, const float* table, const float* coeff,
                                              int grid, int degree, int coeff_per_head, const unsigned long long* rng, float p,
                                              hipStream_t stream) {
-  VITPE_REQUIRE(qkv && out && B >= 0 && N >= 2 && H >= 1);
   VITPE_REQUIRE(rng && drop_p_ok(p));
-  VITPE_REQUIRE(core_check_pe(mode, cos, sin, table, coeff, N, H, grid, degree));
-  if (B == 0) return 0;
-  AttnArgs a{};
-  a.qkv = qkv; a.out = out; a.cos = cos; a.sin = sin; a.table = table; a.coeff = coeff;
-  a.B = B; a.N = N; a.H = H; a.mode = mode; a.grid = grid; a.degree = degree; a.coeff_per_head = coeff_per_head;
-  a.scale = 1.0f / sqrtf((float)HD);
-  if (p > 0.0f) { a.rng = rng; a.drop_thr = drop_threshold(p); a.drop_rs = drop_scale(p); }
-  return dispatch_core(false, dtype, HD, a, stream);
+  return core_entry(false, dtype, qkv, nullptr, out, B, N, H, HD, {mode, cos, sin, table, coeff, grid, degree, coeff_per_head},
+                    nullptr, nullptr, nullptr, rng, p, nullptr, nullptr, nullptr, stream);
 }
 
 // The fused forward at hd = 64 (attn_fused64_fwd_kernel): bf16, 193 <= N <= 208 (13 token tiles), H <= 16 heads of 64.
@@ -354,12 +351,11 @@ extern "C" int vitpe_attention_fused64_fwd(int dtype, const void* xn, const void
                                            hipStream_t stream) {
   VITPE_REQUIRE(xn && wqkv_packed && out && B >= 0);
   if (!vitpe_attention_fused64_supported(dtype, N, H, HD)) return (int)hipErrorNotSupported;
-  VITPE_REQUIRE(core_check_pe(mode, cos, sin, table, coeff, N, H, grid, degree));
+  const PeArgs pe{mode, cos, sin, table, coeff, grid, degree, coeff_per_head};
+  VITPE_REQUIRE(pe_ok(pe, N, H, CORE_HMAX));
   if (B == 0) return 0;
-  AttnArgs a{};
-  a.xn = xn; a.wqkv = wqkv_packed; a.qkv_out = qkv_out; a.out = out; a.cos = cos; a.sin = sin; a.table = table; a.coeff = coeff;
-  a.B = B; a.N = N; a.H = H; a.mode = mode; a.grid = grid; a.degree = degree; a.coeff_per_head = coeff_per_head;
-  a.scale = 1.0f / sqrtf((float)HD);
+  AttnArgs a = attn_args(pe, B, N, H, HD);
+  a.xn = xn; a.wqkv = wqkv_packed; a.qkv_out = qkv_out; a.out = out;
   const dim3 grid_((unsigned)(B * H)), block(64 * F64_NW);
   switch (mode) {
     case PE_RELATIVE: hipLaunchKernelGGL((attn_fused64_fwd_kernel<KM_RELATIVE>), grid_, block, 0, stream, a); break;
@@ -375,18 +371,8 @@ extern "C" int vitpe_attention_core_bwd(int dtype, const void* qkv, const void* 
                                         int HD, int mode, const float* cos, const float* sin, const float* table,
                                         const float* coeff, int grid, int degree, int coeff_per_head, float* dtable,
                                         float* dcoeff, float* dfreqs, hipStream_t stream) {
-  VITPE_REQUIRE(qkv && dout && dqkv && B >= 0 && N >= 2 && H >= 1);
-  VITPE_REQUIRE(core_check_pe(mode, cos, sin, table, coeff, N, H, grid, degree));
-  if (mode == PE_RELATIVE) VITPE_REQUIRE(dtable);
-  if (mode == PE_POLY) VITPE_REQUIRE(dcoeff);
-  if (mode == PE_ROPE_MIXED) VITPE_REQUIRE(dfreqs);
-  if (B == 0) return 0;
-  AttnArgs a{};
-  a.qkv = qkv; a.dout = dout; a.out = dqkv; a.cos = cos; a.sin = sin; a.table = table; a.coeff = coeff;
-  a.dtable = dtable; a.dcoeff = dcoeff; a.dfreqs = dfreqs;
-  a.B = B; a.N = N; a.H = H; a.mode = mode; a.grid = grid; a.degree = degree; a.coeff_per_head = coeff_per_head;
-  a.scale = 1.0f / sqrtf((float)HD);
-  return dispatch_core(true, dtype, HD, a, stream);
+  return core_entry(true, dtype, qkv, dout, dqkv, B, N, H, HD, {mode, cos, sin, table, coeff, grid, degree, coeff_per_head},
+                    dtable, dcoeff, dfreqs, nullptr, 0.0f, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int vitpe_attention_core_bwd_drop(int dtype, const void* qkv, const void* dout, void* dqkv, int B, int N, int H,
@@ -394,20 +380,9 @@ extern "C" int vitpe_attention_core_bwd_drop(int dtype, const void* qkv, const v
                                              const float* coeff, int grid, int degree, int coeff_per_head, float* dtable,
                                              float* dcoeff, float* dfreqs, const unsigned long long* rng, float p,
                                              hipStream_t stream) {
-  VITPE_REQUIRE(qkv && dout && dqkv && B >= 0 && N >= 2 && H >= 1);
   VITPE_REQUIRE(rng && drop_p_ok(p));
-  VITPE_REQUIRE(core_check_pe(mode, cos, sin, table, coeff, N, H, grid, degree));
-  if (mode == PE_RELATIVE) VITPE_REQUIRE(dtable);
-  if (mode == PE_POLY) VITPE_REQUIRE(dcoeff);
-  if (mode == PE_ROPE_MIXED) VITPE_REQUIRE(dfreqs);
-  if (B == 0) return 0;
-  AttnArgs a{};
-  a.qkv = qkv; a.dout = dout; a.out = dqkv; a.cos = cos; a.sin = sin; a.table = table; a.coeff = coeff;
-  a.dtable = dtable; a.dcoeff = dcoeff; a.dfreqs = dfreqs;
-  a.B = B; a.N = N; a.H = H; a.mode = mode; a.grid = grid; a.degree = degree; a.coeff_per_head = coeff_per_head;
-  a.scale = 1.0f / sqrtf((float)HD);
-  if (p > 0.0f) { a.rng = rng; a.drop_thr = drop_threshold(p); a.drop_rs = drop_scale(p); }
-  return dispatch_core(true, dtype, HD, a, stream);
+  return core_entry(true, dtype, qkv, dout, dqkv, B, N, H, HD, {mode, cos, sin, table, coeff, grid, degree, coeff_per_head},
+                    dtable, dcoeff, dfreqs, rng, p, nullptr, nullptr, nullptr, stream);
 }
 
 // The core backward with the gradients w.r.t. the caller's rotary tables (rope-axial: 2-D [P, HD/2]; rope-mixed: 3-D
@@ -419,20 +394,7 @@ extern "C" int vitpe_attention_core_bwd_tables(int dtype, const void* qkv, const
                                                const float* coeff, int grid, int degree, int coeff_per_head, float* dtable,
                                                float* dcoeff, float* dfreqs, float* dcos, float* dsin, float* workspace,
                                                hipStream_t stream) {
-  VITPE_REQUIRE(qkv && dout && dqkv && B >= 0 && N >= 2 && H >= 1);
-  VITPE_REQUIRE(mode == PE_ROPE_AXIAL || mode == PE_ROPE_MIXED);
-  VITPE_REQUIRE(core_check_pe(mode, cos, sin, table, coeff, N, H, grid, degree));
-  VITPE_REQUIRE(dcos && dsin && workspace);
-  (void)dtable; (void)dcoeff; (void)dfreqs;
-  if (B == 0) return 0;
-  AttnArgs a{};
-  a.qkv = qkv; a.dout = dout; a.out = dqkv; a.cos = cos; a.sin = sin;
-  a.tab_slab = workspace;
-  a.B = B; a.N = N; a.H = H; a.mode = mode; a.grid = grid; a.degree = degree; a.coeff_per_head = coeff_per_head;
-  a.scale = 1.0f / sqrtf((float)HD);
-  const int e = dispatch_core(true, dtype, HD, a, stream);
-  if (e) return e;
-  const bool mixed = mode == PE_ROPE_MIXED;
-  const long long L = (long long)(mixed ? H : 1) * (N - 1) * (HD / 2);
-  return reduce_parts(workspace, mixed ? 2 * B : 2 * B * H, L, dcos, dsin, stream);
+  VITPE_REQUIRE(workspace);
+  return core_entry(true, dtype, qkv, dout, dqkv, B, N, H, HD, {mode, cos, sin, table, coeff, grid, degree, coeff_per_head},
+                    dtable, dcoeff, dfreqs, nullptr, 0.0f, dcos, dsin, workspace, stream);
 }

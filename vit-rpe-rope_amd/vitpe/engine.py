@@ -257,6 +257,33 @@ class TrainEngine:
             return K.fused_attention_fwd_wide(x, self.Pkw(blk.attn.qkv.weight), self.H, self.pe, out=out, ln=ln, xn_out=xn_out)
         return K.fused_attention_fwd(x, self.Pk(blk.attn.qkv.weight), self.H, self.pe, out=out, ln=ln, xn_out=xn_out)
 
+    def _attn_layer_fwd(self, l, save_qkv=True):
+        """Layer l's attention forward as the step runs it, on the layer's own buffers: fused (LayerNorm staged inside when
+        fuse_ln), projection + core in one kernel at hd = 64 (save_qkv: the raw projection goes to qkv_l[l] for the
+        backward), or the core on qkv_l[l] -- the qkv Linear in front of that one is the caller's."""
+        blk, a = self.model.blocks[l], self.act[l]
+        if self.fuse_ln:   # (xn1 is None when recompute_ln)
+            return self._attn_fwd(self.x[l], blk, a["a"], ln=(blk.norm1.weight.data, blk.norm1.bias.data, a["m1"], a["r1"]),
+                                  xn_out=a["xn1"])
+        if self.attn_fused:
+            return self._attn_fwd(a["xn1"], blk, a["a"])
+        if self.attn_fused64:
+            return K.attention_fused64_fwd(a["xn1"], self.Fr(blk.attn.qkv.weight), self.H, self.pe,
+                                           qkv_out=(self.qkv_l[l] if save_qkv else None), out=a["a"])
+        return K.attention_core_fwd(self.qkv_l[l], self.H, self.pe, out=a["a"])
+
+    def _attn_bwd(self, l, dout):
+        """Layer l's attention backward as the step runs it: dout (gradient of the merged heads) -> dqkv_l[l], PE-parameter
+        gradients accumulated."""
+        blk, a = self.model.blocks[l], self.act[l]
+        if not self.attn_fused:
+            return K.attention_core_bwd(self.qkv_l[l], dout, self.H, self.pe, out=self.dqkv_l[l], **self.pe_grads)
+        if self.recompute_ln:   # nothing normalised was stored: LayerNorm1 again while staging the raw tokens
+            return K.fused_attention_bwd(self.x[l], self.Pk(blk.attn.qkv.weight), dout, self.H, self.pe, out=self.dqkv_l[l],
+                                         ln=(blk.norm1.weight.data, blk.norm1.bias.data, a["m1"], a["r1"]), **self.pe_grads)
+        return K.fused_attention_bwd(a["xn1"], self.Pk(blk.attn.qkv.weight), dout, self.H, self.pe, out=self.dqkv_l[l],
+                                     **self.pe_grads)
+
     def Fr(self, prm):  # fragment-major packed copy (block_tail2_fwd)
         return self._fr[id(prm)]
 
@@ -372,8 +399,7 @@ class TrainEngine:
             if self.fuse_ln:
                 # LN1 inside the attention kernel's token staging; LN2 inside fc1's operand staging; their
                 # statistics come out of the producing GEMM's epilogue (proj / previous fc2)
-                self._attn_fwd(xin, blk, a["a"], ln=(blk.norm1.weight.data, blk.norm1.bias.data, a["m1"], a["r1"]),
-                               xn_out=a["xn1"])   # (xn1 is None when recompute_ln)
+                self._attn_layer_fwd(l)
                 nxt = (self.act[l + 1]["m1"], self.act[l + 1]["r1"]) if l + 1 < self.Lyr else None
                 eps_next = mdl.blocks[min(l + 1, self.Lyr - 1)].norm1.eps
                 if self.tail2:   # proj + residual + LN2 + MLP branch: one kernel per block tail
@@ -390,14 +416,9 @@ class TrainEngine:
                 continue
             K.layernorm_fwd(xin, blk.norm1.weight.data, blk.norm1.bias.data, blk.norm1.eps, out=a["xn1"],
                             mean=a["m1"], rstd=a["r1"])
-            if self.attn_fused:
-                self._attn_fwd(a["xn1"], blk, a["a"])
-            elif self.attn_fused64:
-                K.attention_fused64_fwd(a["xn1"], self.Fr(blk.attn.qkv.weight), self.H, self.pe,
-                                        qkv_out=(self.qkv_l[l] if self._save_hidden else None), out=a["a"])
-            else:
+            if not self.attn_fused and not self.attn_fused64:
                 K.linear(a["xn1"].view(M, D), self.Sh(blk.attn.qkv.weight), None, out=self.qkv_l[l].view(M, 3 * D))
-                K.attention_core_fwd(self.qkv_l[l], self.H, self.pe, out=a["a"])
+            self._attn_layer_fwd(l, save_qkv=self._save_hidden)
             K.linear(a["a"].view(M, D), self.Sh(blk.attn.proj.weight), blk.attn.proj.bias.data, epi=L.EPI_BIAS_RESID,
                      resid=xin.view(M, D), out=a["xmid"].view(M, D))
             K.layernorm_fwd(a["xmid"], blk.norm2.weight.data, blk.norm2.bias.data, blk.norm2.eps, out=a["xn2"],
@@ -552,14 +573,7 @@ class TrainEngine:
             self._wgrad(lambda: K.gemm_tn(dm, a["a"].view(M, D), G(blk.attn.proj.weight), G(blk.attn.proj.bias)))
             if not tail_done:
                 K.linear(dm, self.St(blk.attn.proj.weight), None, out=self.dtmp.view(M, D))
-            if self.attn_fused and self.recompute_ln:
-                K.fused_attention_bwd(self.x[l], self.Pk(blk.attn.qkv.weight), self.dtmp, self.H, self.pe, out=dqkv,
-                                      ln=(blk.norm1.weight.data, blk.norm1.bias.data, a["m1"], a["r1"]), **self.pe_grads)
-            elif self.attn_fused:
-                K.fused_attention_bwd(a["xn1"], self.Pk(blk.attn.qkv.weight), self.dtmp, self.H, self.pe,
-                                      out=dqkv, **self.pe_grads)
-            else:
-                K.attention_core_bwd(self.qkv_l[l], self.dtmp, self.H, self.pe, out=dqkv, **self.pe_grads)
+            self._attn_bwd(l, self.dtmp)
             self._wgrad(lambda: K.gemm_tn(dqkv.view(M, 3 * D), a["xn1"].view(M, D), G(blk.attn.qkv.weight), None))
             if self.fuse_lnbwd and self.group_wgrad and l > lo:
                 pass   # runs as the prologue of block l - 1's tail backward (next iteration)
@@ -830,44 +844,28 @@ class TrainEngine:
         probes = []
         attn_core_flop = 2 * 2 * N * N * hd * Hh * B
         qkv_flop = 2 * M * D * 3 * D
+        # the step's own attention calls, on every layer's buffers (the backward reads dx_mid[l] where the step reads dtmp)
+        attn_fwd = [(lambda l=l: self._attn_layer_fwd(l)) for l in range(self.Lyr)]
+        attn_bwd = [(lambda l=l: self._attn_bwd(l, self.dx_mid[l])) for l in range(self.Lyr)]
         if self.attn_fused:
-            def fwd(l):
-                blk, a = mdl.blocks[l], self.act[l]
-                if self.fuse_ln:
-                    return lambda: self._attn_fwd(self.x[l], blk, a["a"], ln=(blk.norm1.weight.data, blk.norm1.bias.data,
-                                                                              a["m1"], a["r1"]), xn_out=a["xn1"])
-                return lambda: self._attn_fwd(a["xn1"], blk, a["a"])
-            def bwd(l):
-                blk, a = mdl.blocks[l], self.act[l]
-                if self.recompute_ln:
-                    return lambda: K.fused_attention_bwd(self.x[l], self.Pk(blk.attn.qkv.weight), self.dx_mid[l], Hh, self.pe,
-                                                         out=self.dqkv_l[l], ln=(blk.norm1.weight.data, blk.norm1.bias.data,
-                                                                                 a["m1"], a["r1"]), **self.pe_grads)
-                return lambda: K.fused_attention_bwd(a["xn1"], self.Pk(blk.attn.qkv.weight), self.dx_mid[l], Hh, self.pe,
-                                                     out=self.dqkv_l[l], **self.pe_grads)
             probes.append(dict(name="attn_fwd", kernel=("attn32_fwd_kernel" if self.attn_wide else "attn_fwd_kernel") +
                                " (fused LN1+QKV-project+RoPE+QK^T+softmax+AV)",
-                               fns=[fwd(l) for l in range(self.Lyr)], flop=qkv_flop + attn_core_flop,
+                               fns=attn_fwd, flop=qkv_flop + attn_core_flop,
                                bytes=2 * M * D * es))           # x in, merged heads out (49 920 B / image)
             if not self.fuse_ln:
                 probes[-1]["kernel"] = probes[-1]["kernel"].replace("fused LN1+", "fused ")
             probes.append(dict(name="attn_bwd", kernel="attn_bwd_kernel (recompute + dQ/dK/dV + PE gradients -> d_qkv)",
-                               fns=[bwd(l) for l in range(self.Lyr)], flop=2 * (qkv_flop + attn_core_flop),
+                               fns=attn_bwd, flop=2 * (qkv_flop + attn_core_flop),
                                bytes=(2 + 3) * M * D * es))     # xn, dout in; d_qkv out
         else:
             if self.attn_fused64:   # what the step runs: projection + PE + core in one kernel, raw projection written once
                 probes.append(dict(name="attn_fwd", kernel="attn_fused64_fwd_kernel (QKV-project+RoPE+QK^T+softmax+AV per (image, head), + raw qkv out)",
-                                   fns=[(lambda l=l: K.attention_fused64_fwd(self.act[l]["xn1"], self.Fr(mdl.blocks[l].attn.qkv.weight), Hh,
-                                                                             self.pe, qkv_out=self.qkv_l[l], out=self.act[l]["a"]))
-                                        for l in range(self.Lyr)], flop=qkv_flop + attn_core_flop, bytes=(1 + 3 + 1) * M * D * es))
+                                   fns=attn_fwd, flop=qkv_flop + attn_core_flop, bytes=(1 + 3 + 1) * M * D * es))
             else:
                 probes.append(dict(name="attn_fwd", kernel="attn_core_fwd_kernel (RoPE+QK^T+softmax+AV per (image, head))",
-                                   fns=[(lambda l=l: K.attention_core_fwd(self.qkv_l[l], Hh, self.pe, out=self.act[l]["a"]))
-                                        for l in range(self.Lyr)], flop=attn_core_flop, bytes=4 * M * D * es))
-            probes.append(dict(name="attn_bwd", kernel="attn_core_bwd_kernel",
-                               fns=[(lambda l=l: K.attention_core_bwd(self.qkv_l[l], self.dx_mid[l], Hh, self.pe,
-                                                                      out=self.dqkv_l[l], **self.pe_grads))
-                                    for l in range(self.Lyr)], flop=2 * attn_core_flop, bytes=(3 + 1 + 3) * M * D * es))
+                                   fns=attn_fwd, flop=attn_core_flop, bytes=4 * M * D * es))
+            probes.append(dict(name="attn_bwd", kernel="attn_core_bwd_kernel", fns=attn_bwd, flop=2 * attn_core_flop,
+                               bytes=(3 + 1 + 3) * M * D * es))
         if self.tail2 and self.group_wgrad:
             def tail_f(l):
                 blk, a = mdl.blocks[l], self.act[l]

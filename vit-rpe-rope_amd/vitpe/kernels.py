@@ -315,6 +315,19 @@ class PETables:
         return L.PE_CODES[self.mode]
 
 
+def _pe_tail(pe: PETables):
+    """The positional-encoding operands of every attention entry point, in the C ABI's order."""
+    return (pe.code, ptr(pe.cos), ptr(pe.sin), ptr(pe.table), ptr(pe.coeff), pe.grid, pe.degree, int(pe.coeff_per_head))
+
+
+def _ln_variant(name, ln):
+    """(entry-point name, LayerNorm operands) of a fused attention call: ln=(gamma, beta, mean, rstd) selects the _ln entry."""
+    if ln is None:
+        return name, ()
+    require_device(*ln)
+    return name + "_ln", tuple(ptr(t) for t in ln)
+
+
 def fused_attention_supported(dtype, N, D, HD) -> bool:
     return bool(lib().vitpe_fused_attention_supported(dtype_code(dtype), N, D, HD))
 
@@ -338,18 +351,11 @@ def fused_attention_fwd(xn, wqkv, num_heads, pe: PETables, out=None, ln=None, xn
     HD = D // num_heads
     assert wqkv.numel() == 3 * D * D and wqkv.dtype == xn.dtype
     o = out if out is not None else torch.empty_like(xn)
+    name, lnp = _ln_variant("vitpe_fused_attention_fwd", ln)
     if ln is not None:
-        require_device(*ln)
-        check(lib().vitpe_fused_attention_fwd_ln(dtype_code(xn.dtype), ptr(xn), ptr(ln[0]), ptr(ln[1]), ptr(ln[2]),
-                                                 ptr(ln[3]), ptr(xn_out), ptr(wqkv), ptr(o), B, N, D, HD, pe.code,
-                                                 ptr(pe.cos), ptr(pe.sin), ptr(pe.table), ptr(pe.coeff), pe.grid,
-                                                 pe.degree, int(pe.coeff_per_head), stream_ptr()),
-              "vitpe_fused_attention_fwd_ln")
-        return o
-    check(lib().vitpe_fused_attention_fwd(dtype_code(xn.dtype), ptr(xn), ptr(wqkv), ptr(o), B, N, D, HD, pe.code,
-                                          ptr(pe.cos), ptr(pe.sin), ptr(pe.table), ptr(pe.coeff), pe.grid,
-                                          pe.degree, int(pe.coeff_per_head), stream_ptr()),
-          "vitpe_fused_attention_fwd")
+        lnp += (ptr(xn_out),)
+    check(getattr(lib(), name)(dtype_code(xn.dtype), ptr(xn), *lnp, ptr(wqkv), ptr(o), B, N, D, HD, *_pe_tail(pe),
+                               stream_ptr()), name)
     return o
 
 
@@ -382,9 +388,8 @@ def fused_attention_fwd_wide(xn, wqkv_wide, num_heads, pe: PETables, out=None, l
     if ln is not None:
         require_device(*ln)
     check(lib().vitpe_fused_attention_fwd_wide(dtype_code(xn.dtype), ptr(xn), ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(g[3]),
-                                               ptr(xn_out), ptr(wqkv_wide), ptr(o), B, N, D, HD, pe.code, ptr(pe.cos),
-                                               ptr(pe.sin), ptr(pe.table), ptr(pe.coeff), pe.grid, pe.degree,
-                                               int(pe.coeff_per_head), stream_ptr()), "vitpe_fused_attention_fwd_wide")
+                                               ptr(xn_out), ptr(wqkv_wide), ptr(o), B, N, D, HD, *_pe_tail(pe),
+                                               stream_ptr()), "vitpe_fused_attention_fwd_wide")
     return o
 
 
@@ -395,18 +400,9 @@ def fused_attention_bwd(xn, wqkv, dout, num_heads, pe: PETables, dtable=None, dc
     B, N, D = xn.shape
     HD = D // num_heads
     dqkv = out if out is not None else torch.empty((B, N, 3 * D), dtype=xn.dtype, device=xn.device)
-    if ln is not None:
-        require_device(*ln)
-        check(lib().vitpe_fused_attention_bwd_ln(dtype_code(xn.dtype), ptr(xn), ptr(ln[0]), ptr(ln[1]), ptr(ln[2]),
-                                                 ptr(ln[3]), ptr(wqkv), ptr(dout), ptr(dqkv), B, N, D, HD, pe.code,
-                                                 ptr(pe.cos), ptr(pe.sin), ptr(pe.table), ptr(pe.coeff), pe.grid,
-                                                 pe.degree, int(pe.coeff_per_head), ptr(dtable), ptr(dcoeff),
-                                                 ptr(dfreqs), stream_ptr()), "vitpe_fused_attention_bwd_ln")
-        return dqkv
-    check(lib().vitpe_fused_attention_bwd(dtype_code(xn.dtype), ptr(xn), ptr(wqkv), ptr(dout), ptr(dqkv), B, N, D, HD,
-                                          pe.code, ptr(pe.cos), ptr(pe.sin), ptr(pe.table), ptr(pe.coeff), pe.grid,
-                                          pe.degree, int(pe.coeff_per_head), ptr(dtable), ptr(dcoeff), ptr(dfreqs),
-                                          stream_ptr()), "vitpe_fused_attention_bwd")
+    name, lnp = _ln_variant("vitpe_fused_attention_bwd", ln)
+    check(getattr(lib(), name)(dtype_code(xn.dtype), ptr(xn), *lnp, ptr(wqkv), ptr(dout), ptr(dqkv), B, N, D, HD,
+                               *_pe_tail(pe), ptr(dtable), ptr(dcoeff), ptr(dfreqs), stream_ptr()), name)
     return dqkv
 
 
@@ -421,9 +417,8 @@ def attention_core_fwd(qkv, num_heads, pe: PETables, out=None):
     D = D3 // 3
     HD = D // num_heads
     o = out if out is not None else torch.empty((B, N, D), dtype=qkv.dtype, device=qkv.device)
-    check(lib().vitpe_attention_core_fwd(dtype_code(qkv.dtype), ptr(qkv), ptr(o), B, N, num_heads, HD, pe.code,
-                                         ptr(pe.cos), ptr(pe.sin), ptr(pe.table), ptr(pe.coeff), pe.grid, pe.degree,
-                                         int(pe.coeff_per_head), stream_ptr()), "vitpe_attention_core_fwd")
+    check(lib().vitpe_attention_core_fwd(dtype_code(qkv.dtype), ptr(qkv), ptr(o), B, N, num_heads, HD, *_pe_tail(pe),
+                                         stream_ptr()), "vitpe_attention_core_fwd")
     return o
 
 
@@ -443,8 +438,7 @@ def attention_fused64_fwd(xn, wqkv_pk, num_heads, pe: PETables, qkv_out=None, ou
         assert qkv_out.shape == (B, N, 3 * D) and qkv_out.dtype == xn.dtype and qkv_out.is_contiguous()
     o = out if out is not None else torch.empty_like(xn)
     check(lib().vitpe_attention_fused64_fwd(dtype_code(xn.dtype), ptr(xn), ptr(wqkv_pk), ptr(qkv_out), ptr(o), B, N, num_heads,
-                                            HD, pe.code, ptr(pe.cos), ptr(pe.sin), ptr(pe.table), ptr(pe.coeff), pe.grid,
-                                            pe.degree, int(pe.coeff_per_head), stream_ptr()), "vitpe_attention_fused64_fwd")
+                                            HD, *_pe_tail(pe), stream_ptr()), "vitpe_attention_fused64_fwd")
     return o
 
 
@@ -459,8 +453,7 @@ def attention_core_bwd(qkv, dout, num_heads, pe: PETables, dtable=None, dcoeff=N
     dqkv = out if out is not None else torch.empty_like(qkv)
     if dcos is None and dsin is None:
         check(lib().vitpe_attention_core_bwd(dtype_code(qkv.dtype), ptr(qkv), ptr(dout), ptr(dqkv), B, N, num_heads, HD,
-                                             pe.code, ptr(pe.cos), ptr(pe.sin), ptr(pe.table), ptr(pe.coeff), pe.grid,
-                                             pe.degree, int(pe.coeff_per_head), ptr(dtable), ptr(dcoeff), ptr(dfreqs),
+                                             *_pe_tail(pe), ptr(dtable), ptr(dcoeff), ptr(dfreqs),
                                              stream_ptr()), "vitpe_attention_core_bwd")
         return dqkv
     if dcos is None or dsin is None or pe.cos is None or dcos.shape != pe.cos.shape or dsin.shape != pe.sin.shape:
@@ -468,8 +461,8 @@ def attention_core_bwd(qkv, dout, num_heads, pe: PETables, dtable=None, dcoeff=N
     _f32(dcos, "dcos"), _f32(dsin, "dsin")
     ws = torch.empty(4 * B * num_heads * (N - 1) * (HD // 2), dtype=torch.float32, device=qkv.device)
     check(lib().vitpe_attention_core_bwd_tables(dtype_code(qkv.dtype), ptr(qkv), ptr(dout), ptr(dqkv), B, N, num_heads, HD,
-                                                pe.code, ptr(pe.cos), ptr(pe.sin), None, None, pe.grid, 0, 0, None, None,
-                                                None, ptr(dcos), ptr(dsin), ptr(ws), stream_ptr()),
+                                                *_pe_tail(pe), None, None, None, ptr(dcos), ptr(dsin), ptr(ws),
+                                                stream_ptr()),
           "vitpe_attention_core_bwd_tables")
     return dqkv
 
@@ -555,9 +548,8 @@ def attention_core_fwd_drop(qkv, num_heads, pe: PETables, rng, p, out=None):
     D = D3 // 3
     HD = D // num_heads
     o = out if out is not None else torch.empty((B, N, D), dtype=qkv.dtype, device=qkv.device)
-    check(lib().vitpe_attention_core_fwd_drop(dtype_code(qkv.dtype), ptr(qkv), ptr(o), B, N, num_heads, HD, pe.code,
-                                              ptr(pe.cos), ptr(pe.sin), ptr(pe.table), ptr(pe.coeff), pe.grid, pe.degree,
-                                              int(pe.coeff_per_head), ptr(rng), float(p), stream_ptr()),
+    check(lib().vitpe_attention_core_fwd_drop(dtype_code(qkv.dtype), ptr(qkv), ptr(o), B, N, num_heads, HD,
+                                              *_pe_tail(pe), ptr(rng), float(p), stream_ptr()),
           "vitpe_attention_core_fwd_drop")
     return o
 
@@ -570,8 +562,7 @@ def attention_core_bwd_drop(qkv, dout, num_heads, pe: PETables, rng, p, dtable=N
     HD = D3 // 3 // num_heads
     dqkv = out if out is not None else torch.empty_like(qkv)
     check(lib().vitpe_attention_core_bwd_drop(dtype_code(qkv.dtype), ptr(qkv), ptr(dout), ptr(dqkv), B, N, num_heads, HD,
-                                              pe.code, ptr(pe.cos), ptr(pe.sin), ptr(pe.table), ptr(pe.coeff), pe.grid,
-                                              pe.degree, int(pe.coeff_per_head), ptr(dtable), ptr(dcoeff), ptr(dfreqs),
+                                              *_pe_tail(pe), ptr(dtable), ptr(dcoeff), ptr(dfreqs),
                                               ptr(rng), float(p), stream_ptr()), "vitpe_attention_core_bwd_drop")
     return dqkv
 

@@ -82,67 +82,67 @@ def _fused_ok(xn: Tensor, num_heads: int) -> bool:
     return bool(L.lib().vitpe_fused_attention_supported(L.dtype_code(xn.dtype), N, D, D // num_heads))
 
 
-@torch.library.custom_op("vitpe::attention", mutates_args=())
-def attention(xn: Tensor, wqkv: Tensor, wproj: Tensor, bproj: Tensor, resid: Optional[Tensor], num_heads: int,
-              mode: int, grid: int, pe_param: Optional[Tensor], inv_freq: Optional[Tensor], degree: int,
-              per_head: bool, cos: Optional[Tensor] = None, sin: Optional[Tensor] = None,
-              tables_grad: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
-    """-> (y, a, qkv).  CIFAR geometry: one fused kernel (qkv never leaves the chip, `qkv` is empty; bf16 at N = 65,
-    d = 192, hd = 32: the 32x32-tile kernel); bf16 at hd = 64, N = 197: projection + core in one kernel, `qkv` its side output;
-    other geometries: qkv Linear (panel GEMM) + the per-(image, head) attention core.  cos / sin: caller-supplied rotary tables ([P, hd/2] or [H, P, hd/2]) used instead of the module's own.
-    tables_grad: the caller's tables require grad -- the qkv Linear + core route at every geometry (the fused kernels
-    return no table gradients), so that the backward has `qkv` and runs the core backward with table gradients."""
+def _attention_forward(op: str, one_kernel: bool, xn, wqkv, bqkv, wproj, bproj, resid, num_heads, mode, grid, pe_param,
+                       inv_freq, degree, per_head, cos, sin, tables_grad, attn_p, proj_p, rng):
+    """-> (y, a, qkv), the forward of both attention ops (`op`: the name their errors carry).  one_kernel: the routes
+    that fuse the qkv projection into the attention kernel are allowed (they have no bias input, no dropout and no table
+    gradients); otherwise, and where none of them fits: qkv Linear (panel GEMM) + the per-(image, head) attention core."""
     dt = xn.dtype
     B, N, D = xn.shape
     t = _pe_tables(mode, grid, pe_param, inv_freq, degree, per_head, cos, sin)
-    if tables_grad:
-        if cos is None or MODES[mode] not in ("rope-axial", "rope-mixed"):
-            raise L.VitpeError("vitpe::attention: tables_grad needs caller (cos, sin) tables in a rope mode")
-        qkv = K.linear(xn.contiguous().view(B * N, D), _shadow(wqkv, dt), None, epi=L.EPI_BIAS).view(B, N, 3 * D)
-        a = K.attention_core_fwd(qkv, num_heads, t)
-    elif _fused_ok(xn, num_heads):
+    if tables_grad and attn_p > 0.0:
+        raise NotImplementedError(f"{op}: gradients of caller rotary tables together with attn_drop > 0")
+    if tables_grad and (cos is None or MODES[mode] not in ("rope-axial", "rope-mixed")):
+        raise L.VitpeError(f"{op}: tables_grad needs caller (cos, sin) tables in a rope mode")
+    if (attn_p > 0.0 or proj_p > 0.0) and (rng is None or tuple(rng.shape) != (2, 2)):
+        raise L.VitpeError(f"{op}: dropout needs rng, a [2, 2] int64 device tensor")
+    one_kernel = one_kernel and not tables_grad   # (the backward with table gradients is the core's: it reads qkv)
+    if one_kernel and _fused_ok(xn, num_heads):
         if K.fused_attention_wide_supported(dt, N, D, D // num_heads):
             a = K.fused_attention_fwd_wide(xn.contiguous(), K.pack_qkv_weights_wide(wqkv.contiguous(), dt, num_heads), num_heads, t)
         else:
             a = K.fused_attention_fwd(xn.contiguous(), K.pack_qkv_weights(wqkv.contiguous(), dt, num_heads), num_heads, t)
         qkv = xn.new_empty(0)
-    elif K.attention_fused64_supported(dt, N, num_heads, D // num_heads):
+    elif one_kernel and K.attention_fused64_supported(dt, N, num_heads, D // num_heads):
         # ViT-B/16 geometry: projection + PE + core in one kernel; the raw projection is its side output (the core
         # backward reads it)
         qkv = xn.new_empty((B, N, 3 * D))
         a = K.attention_fused64_fwd(xn.contiguous(), K.pack_weight_frags(wqkv.contiguous().float(), dt, 64, 0), num_heads, t,
                                     qkv_out=qkv)
     else:
-        qkv = K.linear(xn.contiguous().view(B * N, D), _shadow(wqkv, dt), None, epi=L.EPI_BIAS).view(B, N, 3 * D)
-        a = K.attention_core_fwd(qkv, num_heads, t)
-    if resid is None:
+        qkv = K.linear(xn.contiguous().view(B * N, D), _shadow(wqkv, dt), bqkv, epi=L.EPI_BIAS).view(B, N, 3 * D)
+        if attn_p > 0.0:
+            a = K.attention_core_fwd_drop(qkv, num_heads, t, rng[0], attn_p)
+        else:
+            a = K.attention_core_fwd(qkv, num_heads, t)
+    r2 = None if resid is None else resid.contiguous().view(B * N, D)
+    if proj_p > 0.0:
+        y = K.linear(a.view(B * N, D), _shadow(wproj, dt), bproj, epi=L.EPI_BIAS)
+        y = K.dropout_fwd(y, rng[1], proj_p, resid=r2)
+    elif r2 is None:
         y = K.linear(a.view(B * N, D), _shadow(wproj, dt), bproj, epi=L.EPI_BIAS)
     else:
-        y = K.linear(a.view(B * N, D), _shadow(wproj, dt), bproj, epi=L.EPI_BIAS_RESID,
-                      resid=resid.contiguous().view(B * N, D))
+        y = K.linear(a.view(B * N, D), _shadow(wproj, dt), bproj, epi=L.EPI_BIAS_RESID, resid=r2)
     return y.view(B, N, D), a, qkv
 
 
-@attention.register_fake
-def _(xn, wqkv, wproj, bproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos=None, sin=None,
-      tables_grad=False):
-    B, N, D = xn.shape
-    return torch.empty_like(xn), torch.empty_like(xn), xn.new_empty(0)
-
-
-def _attn_setup(ctx, inputs, output):
-    xn, wqkv, wproj, bproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos, sin, tables_grad = inputs
+def _attention_setup(ctx, output, one_kernel, xn, wqkv, bqkv, wproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree,
+                     per_head, cos, sin, tables_grad, attn_p, proj_p, rng):
     _, a, qkv = output
-    ctx.save_for_backward(xn, wqkv, wproj, a, qkv, pe_param, inv_freq, cos, sin)
-    ctx.meta = (num_heads, mode, grid, degree, per_head, resid is not None, tables_grad)
+    ctx.save_for_backward(xn, wqkv, wproj, a, qkv, pe_param, inv_freq, cos, sin, rng)
+    ctx.meta = (one_kernel, num_heads, mode, grid, degree, per_head, resid is not None, tables_grad, bqkv is not None, attn_p,
+                proj_p)
 
 
-def _attn_backward(ctx, dy, _da, _dqkv):
-    xn, wqkv, wproj, a, qkv, pe_param, inv_freq, cos, sin = ctx.saved_tensors
-    num_heads, mode, grid, degree, per_head, has_resid, tables_grad = ctx.meta
+def _attention_backward(ctx, dy):
+    """-> (dxn, dwqkv, dbqkv, dwproj, dbproj, dresid, dpe, dcos, dsin), the backward of both attention ops."""
+    xn, wqkv, wproj, a, qkv, pe_param, inv_freq, cos, sin, rng = ctx.saved_tensors
+    one_kernel, num_heads, mode, grid, degree, per_head, has_resid, tables_grad, has_bqkv, attn_p, proj_p = ctx.meta
     dt = xn.dtype
     B, N, D = xn.shape
     dy2 = dy.contiguous().view(B * N, D)
+    if proj_p > 0.0:   # d(proj output) = dy . m / (1 - p), the proj site's mask regenerated; the residual takes dy itself
+        dy2 = K.dropout_bwd(dy2, rng[1], proj_p)
     # proj: da = dy Wproj ; dWproj = dy^T a ; dbproj = colsum(dy)
     da = K.linear(dy2, _shadow_t(wproj, dt), None, epi=L.EPI_BIAS)
     dwproj = torch.zeros_like(wproj)
@@ -158,11 +158,13 @@ def _attn_backward(ctx, dy, _da, _dqkv):
         pe_grads["dfreqs"] = torch.zeros(2, num_heads, D // num_heads // 2, dtype=torch.float32, device=xn.device)
         dpe = None
     dcos = dsin = None
-    if tables_grad:   # gradients w.r.t. the caller's tables (vitpe_attention_core_bwd_tables), fp32 like t.cos / t.sin
+    if attn_p > 0.0:   # the attention-probability mask regenerated inside the core
+        dqkv = K.attention_core_bwd_drop(qkv, da.view(B, N, D), num_heads, t, rng[0], attn_p, **pe_grads)
+    elif tables_grad:   # gradients w.r.t. the caller's tables (vitpe_attention_core_bwd_tables), fp32 like t.cos / t.sin
         dcos, dsin = torch.zeros_like(t.cos), torch.zeros_like(t.sin)
         dqkv = K.attention_core_bwd(qkv, da.view(B, N, D), num_heads, t, dcos=dcos, dsin=dsin)
         dcos, dsin = dcos.view(cos.shape).to(cos.dtype), dsin.view(sin.shape).to(sin.dtype)
-    elif qkv.numel() == 0:
+    elif one_kernel and qkv.numel() == 0:   # the forward was the kernel that keeps qkv on the chip
         dqkv = K.fused_attention_bwd(xn.contiguous(), K.pack_qkv_weights(wqkv.contiguous(), dt, num_heads),
                                      da.view(B, N, D), num_heads, t, **pe_grads)
     else:
@@ -170,8 +172,41 @@ def _attn_backward(ctx, dy, _da, _dqkv):
     dq2 = dqkv.view(B * N, 3 * D)
     dxn = K.linear(dq2, _shadow_t(wqkv, dt), None, epi=L.EPI_BIAS).view(B, N, D)
     dwqkv = torch.zeros_like(wqkv)
-    K.gemm_tn(dq2, xn.contiguous().view(B * N, D), dwqkv, None)
-    return (dxn, dwqkv, dwproj, dbproj, dy if has_resid else None, None, None, None, dpe, None, None, None, dcos, dsin, None)
+    dbqkv = torch.zeros(3 * D, dtype=torch.float32, device=dy.device) if has_bqkv else None   # gemm_tn's dbias: colsum(dqkv)
+    K.gemm_tn(dq2, xn.contiguous().view(B * N, D), dwqkv, dbqkv)
+    return dxn, dwqkv, dbqkv, dwproj, dbproj, dy if has_resid else None, dpe, dcos, dsin
+
+
+@torch.library.custom_op("vitpe::attention", mutates_args=())
+def attention(xn: Tensor, wqkv: Tensor, wproj: Tensor, bproj: Tensor, resid: Optional[Tensor], num_heads: int,
+              mode: int, grid: int, pe_param: Optional[Tensor], inv_freq: Optional[Tensor], degree: int,
+              per_head: bool, cos: Optional[Tensor] = None, sin: Optional[Tensor] = None,
+              tables_grad: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (y, a, qkv).  CIFAR geometry: one fused kernel (qkv never leaves the chip, `qkv` is empty; bf16 at N = 65,
+    d = 192, hd = 32: the 32x32-tile kernel); bf16 at hd = 64, N = 197: projection + core in one kernel, `qkv` its side output;
+    other geometries: qkv Linear (panel GEMM) + the per-(image, head) attention core.  cos / sin: caller-supplied rotary tables ([P, hd/2] or [H, P, hd/2]) used instead of the module's own.
+    tables_grad: the caller's tables require grad -- the qkv Linear + core route at every geometry (the fused kernels
+    return no table gradients), so that the backward has `qkv` and runs the core backward with table gradients."""
+    return _attention_forward("vitpe::attention", True, xn, wqkv, None, wproj, bproj, resid, num_heads, mode, grid, pe_param,
+                              inv_freq, degree, per_head, cos, sin, tables_grad, 0.0, 0.0, None)
+
+
+@attention.register_fake
+def _(xn, wqkv, wproj, bproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos=None, sin=None,
+      tables_grad=False):
+    B, N, D = xn.shape
+    return torch.empty_like(xn), torch.empty_like(xn), xn.new_empty(0)
+
+
+def _attn_setup(ctx, inputs, output):
+    xn, wqkv, wproj, bproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos, sin, tables_grad = inputs
+    _attention_setup(ctx, output, True, xn, wqkv, None, wproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree,
+                     per_head, cos, sin, tables_grad, 0.0, 0.0, None)
+
+
+def _attn_backward(ctx, dy, _da, _dqkv):
+    dxn, dwqkv, _, dwproj, dbproj, dresid, dpe, dcos, dsin = _attention_backward(ctx, dy)
+    return (dxn, dwqkv, dwproj, dbproj, dresid, None, None, None, dpe, None, None, None, dcos, dsin, None)
 
 
 attention.register_autograd(_attn_backward, setup_context=_attn_setup)
@@ -188,29 +223,8 @@ def attention_drop(xn: Tensor, wqkv: Tensor, bqkv: Optional[Tensor], wproj: Tens
     dropout -> @ v inside the kernel); proj_p > 0: the elementwise dropout kernel behind the proj Linear, residual fused.
     rng: [2, 2] int64 device tensor, the (seed, offset) pairs of the attention-probability site (row 0) and the proj site
     (row 1); the backward regenerates both masks from it.  tables_grad together with attn_p > 0 is refused."""
-    dt = xn.dtype
-    B, N, D = xn.shape
-    t = _pe_tables(mode, grid, pe_param, inv_freq, degree, per_head, cos, sin)
-    if tables_grad and attn_p > 0.0:
-        raise NotImplementedError("vitpe::attention_drop: gradients of caller rotary tables together with attn_drop > 0")
-    if tables_grad and (cos is None or MODES[mode] not in ("rope-axial", "rope-mixed")):
-        raise L.VitpeError("vitpe::attention_drop: tables_grad needs caller (cos, sin) tables in a rope mode")
-    if (attn_p > 0.0 or proj_p > 0.0) and (rng is None or tuple(rng.shape) != (2, 2)):
-        raise L.VitpeError("vitpe::attention_drop: dropout needs rng, a [2, 2] int64 device tensor")
-    qkv = K.linear(xn.contiguous().view(B * N, D), _shadow(wqkv, dt), bqkv, epi=L.EPI_BIAS).view(B, N, 3 * D)
-    if attn_p > 0.0:
-        a = K.attention_core_fwd_drop(qkv, num_heads, t, rng[0], attn_p)
-    else:
-        a = K.attention_core_fwd(qkv, num_heads, t)
-    r2 = None if resid is None else resid.contiguous().view(B * N, D)
-    if proj_p > 0.0:
-        y = K.linear(a.view(B * N, D), _shadow(wproj, dt), bproj, epi=L.EPI_BIAS)
-        y = K.dropout_fwd(y, rng[1], proj_p, resid=r2)
-    elif r2 is None:
-        y = K.linear(a.view(B * N, D), _shadow(wproj, dt), bproj, epi=L.EPI_BIAS)
-    else:
-        y = K.linear(a.view(B * N, D), _shadow(wproj, dt), bproj, epi=L.EPI_BIAS_RESID, resid=r2)
-    return y.view(B, N, D), a, qkv
+    return _attention_forward("vitpe::attention_drop", False, xn, wqkv, bqkv, wproj, bproj, resid, num_heads, mode, grid,
+                              pe_param, inv_freq, degree, per_head, cos, sin, tables_grad, attn_p, proj_p, rng)
 
 
 @attention_drop.register_fake
@@ -223,46 +237,13 @@ def _(xn, wqkv, bqkv, wproj, bproj, resid, num_heads, mode, grid, pe_param, inv_
 def _attn_drop_setup(ctx, inputs, output):
     (xn, wqkv, bqkv, wproj, bproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos, sin, tables_grad,
      attn_p, proj_p, rng) = inputs
-    _, a, qkv = output
-    ctx.save_for_backward(xn, wqkv, wproj, a, qkv, pe_param, inv_freq, cos, sin, rng)
-    ctx.meta = (num_heads, mode, grid, degree, per_head, resid is not None, tables_grad, bqkv is not None, attn_p, proj_p)
+    _attention_setup(ctx, output, False, xn, wqkv, bqkv, wproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree,
+                     per_head, cos, sin, tables_grad, attn_p, proj_p, rng)
 
 
 def _attn_drop_backward(ctx, dy, _da, _dqkv):
-    xn, wqkv, wproj, a, qkv, pe_param, inv_freq, cos, sin, rng = ctx.saved_tensors
-    num_heads, mode, grid, degree, per_head, has_resid, tables_grad, has_bqkv, attn_p, proj_p = ctx.meta
-    dt = xn.dtype
-    B, N, D = xn.shape
-    dy2 = dy.contiguous().view(B * N, D)
-    if proj_p > 0.0:   # d(proj output) = dy . m / (1 - p), the proj site's mask regenerated; the residual takes dy itself
-        dy2 = K.dropout_bwd(dy2, rng[1], proj_p)
-    da = K.linear(dy2, _shadow_t(wproj, dt), None, epi=L.EPI_BIAS)
-    dwproj = torch.zeros_like(wproj)
-    dbproj = torch.zeros(D, dtype=torch.float32, device=dy.device)
-    K.gemm_tn(dy2, a.view(B * N, D), dwproj, dbproj)
-    t = _pe_tables(mode, grid, pe_param, inv_freq, degree, per_head, cos, sin)
-    dpe = torch.zeros_like(pe_param) if pe_param is not None else None
-    name = MODES[mode]
-    pe_grads = dict(dtable=dpe if name == "relative" else None, dcoeff=dpe if name == "polynomial" else None,
-                    dfreqs=dpe if name == "rope-mixed" else None)
-    if cos is not None and name == "rope-mixed":   # caller-supplied tables are constants: the frequency gradient is discarded
-        pe_grads["dfreqs"] = torch.zeros(2, num_heads, D // num_heads // 2, dtype=torch.float32, device=xn.device)
-        dpe = None
-    dcos = dsin = None
-    if attn_p > 0.0:
-        dqkv = K.attention_core_bwd_drop(qkv, da.view(B, N, D), num_heads, t, rng[0], attn_p, **pe_grads)
-    elif tables_grad:
-        dcos, dsin = torch.zeros_like(t.cos), torch.zeros_like(t.sin)
-        dqkv = K.attention_core_bwd(qkv, da.view(B, N, D), num_heads, t, dcos=dcos, dsin=dsin)
-        dcos, dsin = dcos.view(cos.shape).to(cos.dtype), dsin.view(sin.shape).to(sin.dtype)
-    else:
-        dqkv = K.attention_core_bwd(qkv, da.view(B, N, D), num_heads, t, **pe_grads)
-    dq2 = dqkv.view(B * N, 3 * D)
-    dxn = K.linear(dq2, _shadow_t(wqkv, dt), None, epi=L.EPI_BIAS).view(B, N, D)
-    dwqkv = torch.zeros_like(wqkv)
-    dbqkv = torch.zeros(3 * D, dtype=torch.float32, device=dy.device) if has_bqkv else None   # gemm_tn's dbias: colsum(dqkv)
-    K.gemm_tn(dq2, xn.contiguous().view(B * N, D), dwqkv, dbqkv)
-    return (dxn, dwqkv, dbqkv, dwproj, dbproj, dy if has_resid else None, None, None, None, dpe, None, None, None, dcos, dsin,
+    dxn, dwqkv, dbqkv, dwproj, dbproj, dresid, dpe, dcos, dsin = _attention_backward(ctx, dy)
+    return (dxn, dwqkv, dbqkv, dwproj, dbproj, dresid, None, None, None, dpe, None, None, None, dcos, dsin,
             None, None, None, None)
 
 
