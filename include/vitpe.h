@@ -282,6 +282,21 @@ int vitpe_block_tail2_bwd_pre(int dtype, const void* d_qkv, const void* WqT_pack
                               const void* x_mid, const float* mean2, const float* rstd2, const float* gamma, void* du,
                               void* dx_mid, float* dgamma, float* dbeta, const void* WpT_packed, void* da, int M, int D,
                               int HID, vitpe_stream_t stream);
+/* vitpe_tail_cls_fwd / vitpe_tail_cls_bwd: vitpe_block_tail2_fwd (training form: x_mid, LayerNorm2 statistics, xn_out, gp_out,
+ * h_out and out written) and vitpe_block_tail2_bwd on B rows that lie `row_step` rows apart in every [*, .] operand and
+ * statistic: logical row r = row r * row_step of the buffers; no other row is read or written.  The model pools the class
+ * token (vit.py:285: the head reads x[:, 0] alone), so the TOP block's tail (vit.py:116-118,122-124) and its backward
+ * are needed on one row per image: row_step = tokens per image on the [batch x tokens, .] buffers.  Same packed weights,
+ * arithmetic and rounding points as the full-row kernels; a 12-wave workgroup per 16-row tile, columns split over the
+ * waves.  xn_out nullable; gp_out / h_out: both or neither (neither: evaluation).  Any B >= 0.                          */
+int vitpe_tail_cls_fwd(int dtype, const void* attn_out, const void* x_in, const void* Wp_packed, const float* bp,
+                       const float* gamma, const float* beta, void* x_mid, float* mean2, float* rstd2, void* xn_out,
+                       const void* W1_packed, const float* b1, const void* W2_packed, const float* b2, void* gp_out,
+                       void* h_out, void* out, float eps2, int B, int row_step, int D, int HID, vitpe_stream_t stream);
+int vitpe_tail_cls_bwd(int dtype, const void* dy, const void* gp, const void* W2t_packed, const void* W1t_packed,
+                       const void* x_mid, const float* mean2, const float* rstd2, const float* gamma, void* du,
+                       void* dx_mid, float* dgamma, float* dbeta, const void* WpT_packed, void* da, int B, int row_step,
+                       int D, int HID, vitpe_stream_t stream);
 /* vitpe_gemm_tn: dW[N,K] += dY[M,N]^T X[M,K] ; dbias[N] += colsum(dY) (NULL to skip).  fp32
  * outputs, accumulated with atomics over `splits` token slices.                             */
 int vitpe_gemm_tn(int dtype, const void* dY, const void* X, float* dW, float* dbias, int M, int N,
@@ -293,7 +308,10 @@ int vitpe_gemm_tn(int dtype, const void* dY, const void* X, float* dW, float* db
  * descriptors travel as kernel arguments (no device table, graph-capture safe).  Work is cut into
  * (192x192 output block, 64-token stage) units spread evenly over the CUs, so each output block is
  * accumulated (fp32 atomics) by only a handful of workgroups.  N, K multiples of 8 (bf16) / 4 (fp32).  Lists whose every
- * problem has N % 192 == 0 and K % 384 == 0 (bf16, x_op 0: the ViT-B/16 shapes) run on 192 x 384 blocks instead.  */
+ * problem has N % 192 == 0 and K % 384 == 0 (bf16, x_op 0: the ViT-B/16 shapes) run on 192 x 384 blocks instead.
+ * In ANY list, problems with an eighth of the longest problem's stages or fewer are kept out of the placement of the blocks
+ * over the chip (they would cap every other block's row ranges) and run as extra slots of two stages each behind it;
+ * both figures are reasoned, not tuned (csrc/wgrad.hip).                                                              */
 typedef struct {
   const void* dY; /* [M,N] T */
   const void* X;  /* [M,K] T */
@@ -311,6 +329,12 @@ typedef struct {
 #define VITPE_XOP_NONE 0
 #define VITPE_XOP_LAYERNORM 1
 int vitpe_wgrad_group(int dtype, const vitpe_wgrad_problem* problems, int nprob, vitpe_stream_t stream);
+/* ... with a row step per problem (`row_step` HOST array of nprob entries >= 1, or NULL = all 1): logical row m of problem
+ * i's dY, X, x_mean and x_rstd is row m * row_step[i] of the buffers, M counts logical rows.  The top block's fc2 / fc1 /
+ * proj weight gradients contract over the class-token rows only (every other row of their dY is zero: vit.py:285).
+ * Problems much shorter than the longest of the list are kept out of its placement and run as short extra slots.      */
+int vitpe_wgrad_group_rows(int dtype, const vitpe_wgrad_problem* problems, const int* row_step, int nprob,
+                           vitpe_stream_t stream);
 
 /* ---- LayerNorm (nn.LayerNorm(d), eps 1e-5: vit.py:113,116,210) ------------------------------ */
 /* y == NULL: row statistics only (mean and rstd required) */

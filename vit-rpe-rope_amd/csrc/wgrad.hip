@@ -42,6 +42,7 @@ struct WgProb {
   const float* xbeta;
   int M, N, K;
   int xop;
+  int rs;          // row step: logical row m of dY, X and the row statistics lives at row m * rs (1 = dense rows)
   int unit0;       // index of this problem's first work unit
   int nbn;         // 192-wide blocks along N
   int stages;      // ceil(M / RPS)
@@ -54,6 +55,9 @@ struct WgArgs {
   int full_rounds, total_blocks;   // window mode (use_table == 2): whole windows of gridDim.x blocks; blocks in the list
   int tail_rounds;                 // ... and the windows its last, partial window's (row range, block) pairs are dealt over
   int bk;          // block width along K: 192 (wgrad_group_kernel) or 384 (wgrad_wide_kernel)
+  int nbig;        // table / window modes place p[0 .. nbig) only; the SHORT problems p[nbig .. nprob) (an eighth of the longest
+                   // one's stages or less: they would cap the row ranges of all the others) follow as slots of WG_SHORT_SPR stages
+  int short_slots; // ... dealt over the workgroups after their placed work (0 in stream-K mode: its runs cover every unit)
   int range_major; // window mode, lists below two windows: EVERY block is cut into nranges row ranges, the (range, block) pairs
                    // are dealt range-major in full_rounds windows (73 blocks x 7 ranges = 511 of 512 slots: two balanced rounds)
   unsigned long long* census;   // CENSUS build only (vitpe_debug_wgrad_census): s_memtime stamps
@@ -62,6 +66,9 @@ struct WgArgs {
 };
 static_assert(sizeof(WgArgs) <= 4096, "kernel argument block");
 constexpr int WG_CENSUS_STAGES = 24, WG_CENSUS_SLOTS = 4;
+// stages per slot of a short problem (a slot = one partial flush of its block).  Not tuned: 2 and the 1/8 threshold below are
+// the first values tried: neither has been measured against alternatives
+constexpr int WG_SHORT_SPR = 2;
 
 template <typename T> struct WgLayout;
 template <> struct WgLayout<bf16> {
@@ -104,7 +111,27 @@ template <> struct WgLayout<float> {  // exact-fp32 parity mode: padded rows, sc
 // Work assignment shared by the two kernels: calls run(u0, uend) for every contiguous run of work units (one unit = one
 // (output block, 64-row stage)) this workgroup owns.
 template <class RunFn>
+VITPE_DEV void wg_dispatch_placed(const WgArgs& a, RunFn run);
+
+template <class RunFn>
 VITPE_DEV void wg_dispatch(const WgArgs& a, RunFn run) {
+  wg_dispatch_placed(a, run);
+  // short problems (class-row weight gradients: M = batch rows beside M = batch x tokens): slot s = (block, WG_SHORT_SPR stages)
+  for (int s = blockIdx.x; s < a.short_slots; s += gridDim.x) {
+    int q = s, pi = a.nbig;
+    for (int i = a.nbig; i < a.nprob - 1; ++i) {
+      const int nsl = a.p[i].nbn * ((a.p[i].K + a.bk - 1) / a.bk) * ((a.p[i].stages + WG_SHORT_SPR - 1) / WG_SHORT_SPR);
+      if (pi == i && q >= nsl) { q -= nsl; pi = i + 1; }
+    }
+    const WgProb& P = a.p[pi];
+    const int nr = (P.stages + WG_SHORT_SPR - 1) / WG_SHORT_SPR;
+    const int ub = P.unit0 + (q / nr) * P.stages, u0 = ub + (q % nr) * WG_SHORT_SPR;
+    run(u0, min(ub + P.stages, u0 + WG_SHORT_SPR));
+  }
+}
+
+template <class RunFn>
+VITPE_DEV void wg_dispatch_placed(const WgArgs& a, RunFn run) {
   // Window mode (big lists: at least two windows of gridDim.x blocks): every workgroup takes WHOLE blocks, one per round;
   // round r runs the gridDim.x consecutive blocks of window r at the same time and gives each XCD (workgroup id % 8) a
   // contiguous eighth of them -- with the n-blocks of a problem adjacent, the workgroups of an XCD then walk the same token
@@ -135,7 +162,7 @@ VITPE_DEV void wg_dispatch(const WgArgs& a, RunFn run) {
       }
       if (gb >= a.total_blocks) continue;
       int pi = 0, b0 = 0;
-      for (int i = 0; i < a.nprob; ++i) {
+      for (int i = 0; i < a.nbig; ++i) {
         const int nb = a.p[i].nbn * ((a.p[i].K + a.bk - 1) / a.bk);
         if (gb >= b0 + nb) { b0 += nb; pi = i + 1; } else break;
       }
@@ -185,7 +212,7 @@ __global__ __launch_bounds__(768) void wgrad_group_kernel(WgArgs a) {
   struct Cur {
     const T* dY; const T* X; float* dW; float* dbias;
     const float* xmean; const float* xrstd; const float* xgamma; const float* xbeta;
-    int M, N, K, n0, k0, stage, stages, xop;
+    int M, N, K, n0, k0, stage, stages, xop, rs;
   };
   auto decode = [&](int u, Cur& s) {
     int pi = 0;
@@ -198,7 +225,7 @@ __global__ __launch_bounds__(768) void wgrad_group_kernel(WgArgs a) {
     //  updated by other workgroups' flush atomics at the memory side and would miss every time)
     s.xmean = P.xop ? P.xmean : reinterpret_cast<const float*>(P.dY);
     s.xrstd = P.xop ? P.xrstd : reinterpret_cast<const float*>(P.dY);
-    s.xgamma = P.xgamma; s.xbeta = P.xbeta; s.xop = P.xop;
+    s.xgamma = P.xgamma; s.xbeta = P.xbeta; s.xop = P.xop; s.rs = P.rs;
     s.stage = ub - blk * P.stages;
     s.n0 = (blk % P.nbn) * WG_BLK;
     s.k0 = (blk / P.nbn) * a.bk;
@@ -220,17 +247,17 @@ __global__ __launch_bounds__(768) void wgrad_group_kernel(WgArgs a) {
       const int gm = mb + row;
       if (i < 2) {
         const int gn = s.n0 + cc * CHN;
-        rg[i] = (gm < s.M && gn < s.N) ? *reinterpret_cast<const Chunk16*>(s.dY + (size_t)gm * s.N + gn) : zero;
+        rg[i] = (gm < s.M && gn < s.N) ? *reinterpret_cast<const Chunk16*>(s.dY + (size_t)gm * s.rs * s.N + gn) : zero;
       } else {
         const int gk = s.k0 + cc * CHN;
         const bool ok = gm < s.M && gk < s.K;
-        rg[i] = ok ? *reinterpret_cast<const Chunk16*>(s.X + (size_t)gm * s.K + gk) : zero;
+        rg[i] = ok ? *reinterpret_cast<const Chunk16*>(s.X + (size_t)gm * s.rs * s.K + gk) : zero;
         // row statistics: UNCONDITIONAL loads (plain problems read a dummy word of their own dW): a branch around them
         // made the compiler drain the whole prefetch (vmcnt(0)) before it, i.e. every stage waited out its HBM latency
         if (LNX) {
           // (only LOADED here, like the chunks: consuming them now would wait for every load of the burst; unconditional --
           //  plain problems of a mixed list read a dummy word -- because a branch made the compiler drain the prefetch)
-          const int gs = (s.xop == 1) ? min(gm, s.M - 1) : 0;
+          const size_t gs = (s.xop == 1) ? (size_t)min(gm, s.M - 1) * s.rs : 0;
           lnA[i - 2] = s.xrstd[gs];
           lnB[i - 2] = s.xmean[gs];
         }
@@ -551,7 +578,8 @@ static int wgrad_cu_count() {
   return n;
 }
 
-static int wgrad_group_launch(int dtype, const void* problems, int nprob, unsigned long long* census, hipStream_t stream);
+static int wgrad_group_launch(int dtype, const void* problems, const int* row_step, int nprob, unsigned long long* census,
+                              hipStream_t stream);
 // On by default.  (It first ran SLOWER inside the ViT-B/16 step than stand-alone: the single-GPU step hands over all 49
 // problems as launches of 28 + 21, and the placement below -- tuned for 192 x 192 blocks -- sent the 488 wide blocks of the
 // second launch to stream-K and left the first one a 62 %-full last window.  With equal launches (25 + 24) and the tail of
@@ -561,7 +589,14 @@ static bool g_wide_ok = true;
 extern "C" int vitpe_debug_set_wgrad_wide(int on) { g_wide_ok = on != 0; return 0; }
 
 extern "C" int vitpe_wgrad_group(int dtype, const void* problems, int nprob, hipStream_t stream) {
-  return wgrad_group_launch(dtype, problems, nprob, nullptr, stream);
+  return wgrad_group_launch(dtype, problems, nullptr, nprob, nullptr, stream);
+}
+
+// ... with a row step per problem (null: all dense): logical row m of problem i's dY, X and row statistics lives at row
+// m * row_step[i] of the buffers -- a contraction over every row_step-th row (the class-token rows of [batch x tokens, .]
+// tensors) without gathered copies.  M counts the logical rows.
+extern "C" int vitpe_wgrad_group_rows(int dtype, const void* problems, const int* row_step, int nprob, hipStream_t stream) {
+  return wgrad_group_launch(dtype, problems, row_step, nprob, nullptr, stream);
 }
 
 // debug: the same launch (bf16) with per-wave s_memtime stamps of the first 24 stages of every workgroup:
@@ -569,10 +604,11 @@ extern "C" int vitpe_wgrad_group(int dtype, const void* problems, int nprob, hip
 extern "C" int vitpe_debug_wgrad_census(int dtype, const void* problems, int nprob, unsigned long long* census,
                                         hipStream_t stream) {
   VITPE_REQUIRE(census != nullptr && dtype == 1);
-  return wgrad_group_launch(dtype, problems, nprob, census, stream);
+  return wgrad_group_launch(dtype, problems, nullptr, nprob, census, stream);
 }
 
-static int wgrad_group_launch(int dtype, const void* problems, int nprob, unsigned long long* census, hipStream_t stream) {
+static int wgrad_group_launch(int dtype, const void* problems, const int* row_step, int nprob, unsigned long long* census,
+                              hipStream_t stream) {
   VITPE_REQUIRE(problems && nprob >= 0 && nprob <= WG_MAXPROB && (dtype == 0 || dtype == 1));
   const vitpe_wgrad_problem_abi* pr = reinterpret_cast<const vitpe_wgrad_problem_abi*>(problems);
   const int RPS = dtype == 1 ? 64 : 32, CHN = dtype == 1 ? 8 : 4;
@@ -581,27 +617,42 @@ static int wgrad_group_launch(int dtype, const void* problems, int nprob, unsign
   // 192 x 384 blocks (wgrad_wide_kernel) when every problem allows them: bf16, plain X operand, whole blocks
   bool wide = g_wide_ok && dtype == 1 && census == nullptr && nprob > 0;
   for (int i = 0; i < nprob; ++i)
-    wide = wide && (pr[i].M == 0 || (pr[i].x_op == 0 && pr[i].N % WG_BLK == 0 && pr[i].K % WW_BK == 0));
+    wide = wide && (pr[i].M == 0 || (pr[i].x_op == 0 && pr[i].N % WG_BLK == 0 && pr[i].K % WW_BK == 0 &&
+                                     (row_step == nullptr || row_step[i] <= 1)));
   a.bk = wide ? WW_BK : WG_BLK;
-  int units = 0, np = 0;
-  for (int i = 0; i < nprob; ++i) {
-    const vitpe_wgrad_problem_abi& p = pr[i];
-    VITPE_REQUIRE(p.dY && p.X && p.dW && p.M >= 0 && p.N > 0 && p.K > 0 && p.N % CHN == 0 && p.K % CHN == 0);
-    if (p.M == 0) continue;
-    WgProb& q = a.p[np++];
-    VITPE_REQUIRE(p.x_op == 0 || (p.x_op == 1 && p.x_mean && p.x_rstd && p.x_gamma && p.x_beta));
-    q.dY = p.dY; q.X = p.X; q.dW = p.dW; q.dbias = p.dbias; q.M = p.M; q.N = p.N; q.K = p.K;
-    q.xop = p.x_op; q.xmean = p.x_mean; q.xrstd = p.x_rstd; q.xgamma = p.x_gamma; q.xbeta = p.x_beta;
-    q.unit0 = units;
-    q.nbn = (p.N + WG_BLK - 1) / WG_BLK;
-    q.stages = (p.M + RPS - 1) / RPS;
-    const long long nu = (long long)q.nbn * ((p.K + a.bk - 1) / a.bk) * q.stages;
-    VITPE_REQUIRE(units + nu < (1LL << 30));
-    units += (int)nu;
+  // long problems first, the short ones (an eighth of the longest one's stages or less) behind them: the placement below
+  // works on the long ones, whose row ranges the short ones would otherwise cap (R <= min_stages / 4)
+  int max_stages = 0;
+  for (int i = 0; i < nprob; ++i) max_stages = (pr[i].M + RPS - 1) / RPS > max_stages ? (pr[i].M + RPS - 1) / RPS : max_stages;
+  int units = 0, np = 0, nbig = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int i = 0; i < nprob; ++i) {
+      const vitpe_wgrad_problem_abi& p = pr[i];
+      VITPE_REQUIRE(p.dY && p.X && p.dW && p.M >= 0 && p.N > 0 && p.K > 0 && p.N % CHN == 0 && p.K % CHN == 0);
+      VITPE_REQUIRE(row_step == nullptr || row_step[i] >= 1);
+      if (p.M == 0) continue;
+      const int stages = (p.M + RPS - 1) / RPS;
+      if ((stages * 8 <= max_stages) != (pass == 1)) continue;
+      WgProb& q = a.p[np++];
+      VITPE_REQUIRE(p.x_op == 0 || (p.x_op == 1 && p.x_mean && p.x_rstd && p.x_gamma && p.x_beta));
+      q.dY = p.dY; q.X = p.X; q.dW = p.dW; q.dbias = p.dbias; q.M = p.M; q.N = p.N; q.K = p.K;
+      q.xop = p.x_op; q.xmean = p.x_mean; q.xrstd = p.x_rstd; q.xgamma = p.x_gamma; q.xbeta = p.x_beta;
+      q.rs = row_step != nullptr ? row_step[i] : 1;
+      q.unit0 = units;
+      q.nbn = (p.N + WG_BLK - 1) / WG_BLK;
+      q.stages = stages;
+      const long long nu = (long long)q.nbn * ((p.K + a.bk - 1) / a.bk) * q.stages;
+      VITPE_REQUIRE(units + nu < (1LL << 30));
+      units += (int)nu;
+    }
+    if (pass == 0) nbig = np;
   }
   if (units == 0) return 0;
   a.nprob = np;
+  a.nbig = nbig;
   a.total_units = units;
+  const int np_all = np;
+  np = nbig;     // the placement below sees the long problems only
   const int ncu = wgrad_cu_count();
   int grid = 0;
   // ---- table mode: (block, row range) per workgroup, operand-sharing blocks co-located on one XCD -----------
@@ -689,6 +740,11 @@ static int wgrad_group_launch(int dtype, const void* problems, int nprob, unsign
       (void)bestk;
     }
   }
+  if (a.use_table) {
+    for (int i = nbig; i < np_all; ++i)
+      a.short_slots += a.p[i].nbn * ((a.p[i].K + a.bk - 1) / a.bk) * ((a.p[i].stages + WG_SHORT_SPR - 1) / WG_SHORT_SPR);
+  }
+  np = np_all;
   if (!a.use_table) {
     const int wgs = units < ncu ? units : ncu;
     a.units_per_wg = (units + wgs - 1) / wgs;

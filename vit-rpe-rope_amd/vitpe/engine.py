@@ -333,6 +333,16 @@ class TrainEngine:
         # three small kernels: its class loop serialised ten wave reductions per image).  VITPE_FUSE_HEAD=0: three kernels.
         self.fuse_head = self.Cn <= 64 and self.D <= 768 and os.environ.get("VITPE_FUSE_HEAD", "1") == "1"
         self.head_ws = (f(B, D), f(B, D), f(B))
+        # Class-row mode of the TOP block ("Top block on the class-token rows").  The model pools the class token (vit.py: the head reads x[:, 0]): of
+        # x[L] only row b * N is read, of dx_out[L] only that row is non-zero, so the top block's tail, its backward and its
+        # fc2 / fc1 / proj weight gradients run on the B class rows (csrc/tail_cls.hip, row-step problems in csrc/wgrad.hip).
+        # The invariant that replaces the zeros the full-row backward used to write: the non-class rows of du_l[L-1],
+        # dx_mid[L-1] and da_top are zeroed HERE and never written again (the attention backward, the block below's prologue
+        # and the qkv weight gradient sum over all rows).  VITPE_CLS_ROWS=0: the full-row kernels.
+        # (not for a one-layer model: its top block's du_l[0] is self.du, which bench.py's probes write in full)
+        self.cls_rows = (self.tail2 and self.group_wgrad and self.fuse_head and T == torch.bfloat16 and self.Lyr >= 2
+                         and os.environ.get("VITPE_CLS_ROWS", "1") == "1")
+        self._probe_scratch = None
         self.ws_dyn = f(B, D)
         # Gradient tensors read by the weight-gradient GEMMs get per-layer buffers (dy = d x_out, dmid = d x_mid,
         # du, dqkv): the grouped weight-gradient launch at the end of a backward part reads all of them, so the main
@@ -345,6 +355,15 @@ class TrainEngine:
         self.dqkv_l = [e(B, N, 3 * D) for _ in range(self.Lyr)]
         self.qkv_l = [] if self.attn_fused else [e(B, N, 3 * D) for _ in range(self.Lyr)]
         self.dqkv, self.du = self.dqkv_l[0], self.du_l[0]          # (bench.py times the kernels on these)
+        self.da_top = None
+        if self.cls_rows:
+            # the top block's own d(attention output): dtmp is shared with the layers below, which overwrite every row
+            self.da_top = torch.zeros(B, N, D, dtype=T, device=dev)
+            top = self.act[self.Lyr - 1]
+            for t in (self.du_l[self.Lyr - 1], self.dx_mid[self.Lyr - 1], self.x[self.Lyr], top["xmid"], top["m2"], top["r2"],
+                      top["u"], top["h"], top["xn2"]):
+                if t is not None:   # (forward side: no kernel reads their non-class rows; a stray read finds finite zeros)
+                    t.zero_()
         self.dataset, self.batch_idx = None, None
         self._wg_groups = {}
         self.dpatch = e(B * self.P, D)
@@ -431,24 +450,49 @@ class TrainEngine:
             K.head_fwd(self.x[-1], mdl.norm.weight.data, mdl.norm.bias.data, mdl.head.weight.data, mdl.head.bias.data,
                        mdl.norm.eps, save=True, logits=self.logits, ws=self.head_ws)
 
-    def _block_tail_fwd(self, l, blk, a, nxt, save=None):
-        """save: keep gelu'(u) and gelu(u) for the backward (None: what the running _forward was asked for)."""
+    def _top_cls(self, l):
+        return self.cls_rows and l == self.Lyr - 1
+
+    def _block_tail_fwd(self, l, blk, a, nxt, save=None, scratch=None):
+        """save: keep gelu'(u) and gelu(u) for the backward (None: what the running _forward was asked for).
+        scratch (kernel_probes, class-row mode): the FULL-row kernel of the top block, its outputs sent to these buffers."""
         M, D = self.M, self.D
         eps_next = self.model.blocks[min(l + 1, self.Lyr - 1)].norm1.eps
         if save is None:
             save = self._save_hidden
+        if self._top_cls(l) and scratch is None:   # the class rows only, in place on the full-layout buffers
+            K.tail_cls_fwd(a["a"].view(M, D), self.x[l].view(M, D), self.Fr(blk.attn.proj.weight), blk.attn.proj.bias.data,
+                           blk.norm2.weight.data, blk.norm2.bias.data, self.Fr(blk.mlp.fc1.weight), blk.mlp.fc1.bias.data,
+                           self.Fr(blk.mlp.fc2.weight), blk.mlp.fc2.bias.data, self.B, self.N, a["xmid"].view(M, D), a["m2"],
+                           a["r2"], self.x[l + 1].view(M, D),
+                           xn_out=(a["xn2"].view(M, D) if (save and not self.recompute_ln) else None),
+                           gp=(a["u"].view(torch.float16) if save else None), h=(a["h"] if save else None), eps2=blk.norm2.eps)
+            return
+        o = scratch if scratch is not None else dict(a, xout=self.x[l + 1])
         K.block_tail2_fwd(a["a"].view(M, D), self.x[l].view(M, D), self.Fr(blk.attn.proj.weight),
                           blk.attn.proj.bias.data, blk.norm2.weight.data, blk.norm2.bias.data,
                           self.Fr(blk.mlp.fc1.weight), blk.mlp.fc1.bias.data, self.Fr(blk.mlp.fc2.weight),
-                          blk.mlp.fc2.bias.data, x_mid=a["xmid"].view(M, D), mean2=a["m2"], rstd2=a["r2"],
-                          xn_out=(a["xn2"].view(M, D) if (save and not self.recompute_ln) else None),
-                          gp=(a["u"].view(torch.float16) if save else None), h=(a["h"] if save else None), out=self.x[l + 1].view(M, D),
+                          blk.mlp.fc2.bias.data, x_mid=o["xmid"].view(M, D), mean2=o["m2"], rstd2=o["r2"],
+                          xn_out=(o["xn2"].view(M, D) if (save and not self.recompute_ln) else None),
+                          gp=(o["u"].view(torch.float16) if save else None), h=(o["h"] if save else None), out=o["xout"].view(M, D),
                           stats=nxt, eps2=blk.norm2.eps, eps_next=eps_next, save=save)
 
-    def _block_tail_bwd(self, l, blk, a, pre=False):
+    def _block_tail_bwd(self, l, blk, a, pre=False, scratch=None):
         """pre: the qkv data gradient + LayerNorm1 backward of block l + 1 run first in the same kernel and produce
-        dx_out[l + 1] (this block's dy)."""
+        dx_out[l + 1] (this block's dy).  scratch: as in _block_tail_fwd."""
         M, D, G = self.M, self.D, self.Gr
+        if self._top_cls(l) and scratch is None:
+            K.tail_cls_bwd(self.dx_out[l + 1].view(M, D), a["u"].view(torch.float16), self.Frt(blk.mlp.fc2.weight),
+                           self.Frt(blk.mlp.fc1.weight), a["xmid"].view(M, D), a["m2"], a["r2"], blk.norm2.weight.data,
+                           G(blk.norm2.weight), G(blk.norm2.bias), self.Frt(blk.attn.proj.weight), self.B, self.N,
+                           du=self.du_l[l], out=self.dx_mid[l].view(M, D), da=self.da_top.view(M, D))
+            return
+        if scratch is not None:
+            K.block_tail2_bwd(self.dx_out[l + 1].view(M, D), scratch["u"].view(torch.float16), self.Frt(blk.mlp.fc2.weight),
+                              self.Frt(blk.mlp.fc1.weight), scratch["xmid"].view(M, D), scratch["m2"], scratch["r2"],
+                              blk.norm2.weight.data, G(blk.norm2.weight), G(blk.norm2.bias), self.Frt(blk.attn.proj.weight),
+                              du=scratch["du"], out=scratch["dxmid"].view(M, D), da=self.dtmp.view(M, D))
+            return
         if pre:
             up, ua = self.model.blocks[l + 1], self.act[l + 1]
             K.block_tail2_bwd_pre(self.dqkv_l[l + 1].view(M, 3 * D), self.Frt(up.attn.qkv.weight), self.x[l + 1].view(M, D),
@@ -500,8 +544,11 @@ class TrainEngine:
             else:
                 fc1 = (self.du_l[l], a["xn2"].view(M, D), G(blk.mlp.fc1.weight), G(blk.mlp.fc1.bias))
                 qkv = (self.dqkv_l[l].view(M, 3 * D), a["xn1"].view(M, D), G(blk.attn.qkv.weight), None)
-            probs += [(self.dx_out[l + 1].view(M, D), a["h"], G(blk.mlp.fc2.weight), G(blk.mlp.fc2.bias)), fc1,
-                      (self.dx_mid[l].view(M, D), a["a"].view(M, D), G(blk.attn.proj.weight), G(blk.attn.proj.bias)), qkv]
+            fc2 = (self.dx_out[l + 1].view(M, D), a["h"], G(blk.mlp.fc2.weight), G(blk.mlp.fc2.bias))
+            proj = (self.dx_mid[l].view(M, D), a["a"].view(M, D), G(blk.attn.proj.weight), G(blk.attn.proj.bias))
+            if self._top_cls(l):   # their dY is zero outside the class rows: contract over rows b * N only (row step N)
+                fc2, fc1, proj = ((p + (None,) * (5 - len(p)) + (self.N,)) for p in (fc2, fc1, proj))
+            probs += [fc2, fc1, proj, qkv]
         if with_embed:
             probs.append((self.dpatch, self.patches, G(mdl.patch_embed.weight).view(D, -1), G(mdl.patch_embed.bias)))
         return probs
@@ -573,7 +620,7 @@ class TrainEngine:
             self._wgrad(lambda: K.gemm_tn(dm, a["a"].view(M, D), G(blk.attn.proj.weight), G(blk.attn.proj.bias)))
             if not tail_done:
                 K.linear(dm, self.St(blk.attn.proj.weight), None, out=self.dtmp.view(M, D))
-            self._attn_bwd(l, self.dtmp)
+            self._attn_bwd(l, self.da_top if self._top_cls(l) else self.dtmp)
             self._wgrad(lambda: K.gemm_tn(dqkv.view(M, 3 * D), a["xn1"].view(M, D), G(blk.attn.qkv.weight), None))
             if self.fuse_lnbwd and self.group_wgrad and l > lo:
                 pass   # runs as the prologue of block l - 1's tail backward (next iteration)
@@ -867,13 +914,26 @@ class TrainEngine:
             probes.append(dict(name="attn_bwd", kernel="attn_core_bwd_kernel", fns=attn_bwd, flop=2 * attn_core_flop,
                                bytes=(3 + 1 + 3) * M * D * es))
         if self.tail2 and self.group_wgrad:
+            def scr(l):
+                # class-row mode: the probes time the FULL-row kernels, which write every row -- on the top block's live buffers
+                # that would break the zero invariant of every later step, so its launches write to buffers of their own
+                if not self._top_cls(l):
+                    return None
+                if self._probe_scratch is None:
+                    z = lambda *s, dt=self.T: torch.zeros(*s, dtype=dt, device=self.dev)  # noqa: E731
+                    zf = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.dev)  # noqa: E731
+                    self._probe_scratch = dict(xmid=z(B, N, D), m2=zf(M), r2=zf(M), u=z(M, hid), h=z(M, hid),
+                                               xn2=(None if self.recompute_ln else z(B, N, D)), xout=z(B, N, D),
+                                               du=z(M, hid), dxmid=z(B, N, D))
+                return self._probe_scratch
             def tail_f(l):
                 blk, a = mdl.blocks[l], self.act[l]
                 nxt = (self.act[l + 1]["m1"], self.act[l + 1]["r1"]) if l + 1 < self.Lyr else None
-                return lambda: self._block_tail_fwd(l, blk, a, nxt, save=True)   # the TRAINING instantiation, whatever ran last
+                sc = scr(l)
+                return lambda: self._block_tail_fwd(l, blk, a, nxt, save=True, scratch=sc)   # the TRAINING instantiation, whatever ran last
             def tail_b(l):
-                blk, a = mdl.blocks[l], self.act[l]
-                return lambda: self._block_tail_bwd(l, blk, a)
+                blk, a, sc = mdl.blocks[l], self.act[l], scr(l)
+                return lambda: self._block_tail_bwd(l, blk, a, scratch=sc)
             tail_flop = 2 * M * D * D + 2 * 2 * M * D * hid
             probes.append(dict(name="block_tail_fwd",
                                kernel="block_tail2_fwd_kernel" +

@@ -219,6 +219,48 @@ def block_tail2_bwd_pre(dqkv, wqt_pk, x1, mean1, rstd1, gamma1, dres1, dgamma1, 
     return out, du, da
 
 
+def tail_cls_fwd(attn_out, x_in, wp_pk, bp, gamma, beta, w1_pk, b1, w2_pk, b2, B, row_step, x_mid, mean2, rstd2, out,
+                 xn_out=None, gp=None, h=None, eps2=1e-5):
+    """block_tail2_fwd on the B rows r * row_step of the full-layout buffers (include/vitpe.h: vitpe_tail_cls_fwd), in place:
+    every other row of x_mid / mean2 / rstd2 / xn_out / gp / h / out keeps what it held.  gp and h: both (training) or
+    neither (evaluation)."""
+    require_device(attn_out, x_in, wp_pk, bp, gamma, beta, w1_pk, b1, w2_pk, b2, x_mid, mean2, rstd2, xn_out, gp, h, out)
+    M, D = attn_out.shape
+    HID = b1.numel()
+    assert row_step >= 1 and (B == 0 or (B - 1) * row_step < M)
+    assert x_in.shape == x_mid.shape == out.shape == (M, D) and mean2.numel() == M and rstd2.numel() == M
+    assert wp_pk.numel() == D * D and w1_pk.numel() == HID * D and w2_pk.numel() == D * HID
+    assert attn_out.dtype == x_in.dtype == wp_pk.dtype == w1_pk.dtype == w2_pk.dtype == x_mid.dtype == out.dtype
+    assert xn_out is None or (xn_out.shape == (M, D) and xn_out.dtype == attn_out.dtype)
+    assert (gp is None) == (h is None)
+    if gp is not None:
+        assert gp.shape == h.shape == (M, HID) and h.dtype == attn_out.dtype and gp.dtype == torch.float16
+    for t_, n_ in ((bp, "bp"), (gamma, "gamma"), (beta, "beta"), (b1, "b1"), (b2, "b2"), (mean2, "mean2"), (rstd2, "rstd2")):
+        _f32(t_, n_)
+    check(lib().vitpe_tail_cls_fwd(dtype_code(attn_out.dtype), ptr(attn_out), ptr(x_in), ptr(wp_pk), ptr(bp), ptr(gamma),
+                                   ptr(beta), ptr(x_mid), ptr(mean2), ptr(rstd2), ptr(xn_out), ptr(w1_pk), ptr(b1),
+                                   ptr(w2_pk), ptr(b2), ptr(gp), ptr(h), ptr(out), float(eps2), int(B), int(row_step), D, HID,
+                                   stream_ptr()), "vitpe_tail_cls_fwd")
+
+
+def tail_cls_bwd(dy, gp, w2t_pk, w1t_pk, x_mid, mean2, rstd2, gamma, dgamma, dbeta, wpt_pk, B, row_step, du, out, da):
+    """block_tail2_bwd on the B rows r * row_step of the full-layout buffers (vitpe_tail_cls_bwd), in place: every other row
+    of du / out (= d x_mid) / da keeps what it held; dgamma / dbeta accumulated."""
+    require_device(dy, gp, w2t_pk, w1t_pk, x_mid, mean2, rstd2, gamma, dgamma, dbeta, wpt_pk, du, out, da)
+    M, D = dy.shape
+    HID = gp.shape[1]
+    assert row_step >= 1 and (B == 0 or (B - 1) * row_step < M)
+    assert gp.shape == du.shape == (M, HID) and x_mid.shape == out.shape == da.shape == (M, D)
+    assert mean2.numel() == M and rstd2.numel() == M and w2t_pk.numel() == HID * D and w1t_pk.numel() == HID * D
+    assert wpt_pk.numel() == D * D
+    assert dy.dtype == w2t_pk.dtype == w1t_pk.dtype == x_mid.dtype == wpt_pk.dtype == du.dtype == out.dtype == da.dtype
+    assert gp.dtype == torch.float16
+    _f32(gamma, "gamma"), _f32(dgamma, "dgamma"), _f32(dbeta, "dbeta"), _f32(mean2, "mean2"), _f32(rstd2, "rstd2")
+    check(lib().vitpe_tail_cls_bwd(dtype_code(dy.dtype), ptr(dy), ptr(gp), ptr(w2t_pk), ptr(w1t_pk), ptr(x_mid), ptr(mean2),
+                                   ptr(rstd2), ptr(gamma), ptr(du), ptr(out), ptr(dgamma), ptr(dbeta), ptr(wpt_pk), ptr(da),
+                                   int(B), int(row_step), D, HID, stream_ptr()), "vitpe_tail_cls_bwd")
+
+
 class _WgradProblem(ctypes.Structure):   # include/vitpe.h: vitpe_wgrad_problem
     _fields_ = [("dY", ctypes.c_void_p), ("X", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("dbias", ctypes.c_void_p),
                 ("M", ctypes.c_int), ("N", ctypes.c_int), ("K", ctypes.c_int), ("x_op", ctypes.c_int),
@@ -227,27 +269,34 @@ class _WgradProblem(ctypes.Structure):   # include/vitpe.h: vitpe_wgrad_problem
 
 
 class WgradGroup:
-    """A fixed list of weight-gradient problems (dY [M,N], X [M,K], dW [N,K] fp32, dbias [N] fp32 | None[, ln]),
+    """A fixed list of weight-gradient problems (dY [M,N], X [M,K], dW [N,K] fp32, dbias [N] fp32 | None[, ln[, row_step]]),
     launched together by one vitpe_wgrad_group call.  The tensors are referenced, not copied.  The optional fifth
     element ln = (mean [M], rstd [M], gamma [K], beta [K]) makes the operand LayerNorm(X), recomputed inside the kernel
-    from the raw rows X (the normalised tensor is never stored)."""
+    from the raw rows X (the normalised tensor is never stored).  The optional sixth element row_step > 1 contracts over
+    rows 0, row_step, 2 row_step, ... of dY, X and the statistics only (ceil(M / row_step) logical rows)."""
 
     MAX = 28
 
     def __init__(self, problems):
-        problems = [tuple(p) + (None,) * (5 - len(p)) for p in problems]
+        problems = [tuple(p) + (None,) * (6 - len(p)) for p in problems]
         if not 0 < len(problems) <= self.MAX:
             raise L.VitpeError(f"WgradGroup takes 1..{self.MAX} problems, got {len(problems)}")
-        self.keep = [p[:4] for p in problems]
+        # (what the kernel contracts over: the strided views of a row-step problem)
+        self.keep = [(p[0][::p[5]], p[1][::p[5]]) + p[2:4] if p[5] else p[:4] for p in problems]
+        self._full = [p[:2] for p in problems]
         self._ln = [p[4] for p in problems]
         self.dtype = problems[0][0].dtype
         self.arr = (_WgradProblem * len(problems))()
-        for i, (dy, x, dw, db, ln) in enumerate(problems):
+        self.steps = (ctypes.c_int * len(problems))(*[int(p[5] or 1) for p in problems])
+        self.strided = any(st != 1 for st in self.steps)
+        for i, (dy, x, dw, db, ln, rs) in enumerate(problems):
             require_device(dy, x, dw, db)
-            M, N = dy.shape
+            rs = int(rs or 1)
+            Mfull, N = dy.shape
             K = x.shape[1]
-            assert x.shape[0] == M and dw.numel() == N * K and dy.dtype == x.dtype == self.dtype
+            assert rs >= 1 and x.shape[0] == Mfull and dw.numel() == N * K and dy.dtype == x.dtype == self.dtype
             assert dy.is_contiguous() and x.is_contiguous() and dw.is_contiguous()
+            M = -(-Mfull // rs)
             _f32(dw, "dw"), _f32(db, "dbias")
             if ln is None:
                 self.arr[i] = _WgradProblem(ptr(dy), ptr(x), ptr(dw), ptr(db), M, N, K, 0, None, None, None, None)
@@ -256,11 +305,15 @@ class WgradGroup:
                 require_device(mean, rstd, gamma, beta)
                 for t_, n_ in ((mean, "mean"), (rstd, "rstd"), (gamma, "gamma"), (beta, "beta")):
                     _f32(t_, n_)
-                assert mean.numel() == M and rstd.numel() == M and gamma.numel() == K and beta.numel() == K
+                assert mean.numel() == Mfull and rstd.numel() == Mfull and gamma.numel() == K and beta.numel() == K
                 self.arr[i] = _WgradProblem(ptr(dy), ptr(x), ptr(dw), ptr(db), M, N, K, 1, ptr(mean), ptr(rstd), ptr(gamma),
                                             ptr(beta))
 
     def launch(self):
+        if self.strided:
+            check(lib().vitpe_wgrad_group_rows(dtype_code(self.dtype), ctypes.addressof(self.arr), ctypes.addressof(self.steps),
+                                               len(self.arr), stream_ptr()), "vitpe_wgrad_group_rows")
+            return
         check(lib().vitpe_wgrad_group(dtype_code(self.dtype), ctypes.addressof(self.arr), len(self.arr), stream_ptr()),
               "vitpe_wgrad_group")
 
