@@ -183,6 +183,20 @@ int vitpe_drop_path_fwd(int dtype, const void* x, const void* resid, void* y, in
                         const unsigned long long* rng, float p, vitpe_stream_t stream);
 int vitpe_drop_path_bwd(int dtype, const void* dy, void* dx, int B, long long per, const unsigned long long* rng, float p,
                         vitpe_stream_t stream);
+/* vitpe_branch_drop_fwd: one residual branch's elementwise dropout, per-sample drop-path and residual add in one pass over
+ *   [B, per]: y = [resid +] f_b * round_T(x . m_e / (1 - p_elem)), f_b = m_b / (1 - p_path); m_e on the flat element index
+ *   (as vitpe_dropout_fwd), m_b on e = b (as vitpe_drop_path_fwd).  Bit for bit vitpe_dropout_fwd followed by
+ *   vitpe_drop_path_fwd on the same pairs.  A NULL rng_elem / rng_path leaves that site out (its p is then ignored) and the
+ *   result is that of the single remaining kernel; both NULL, per % 4 != 0 or B > 2^24: hipErrorInvalidValue, nothing is
+ *   launched.  vitpe_branch_drop_bwd: dx = the same factors on dy (the forward without a residual).
+ * vitpe_rng_advance: offset += inc (mod 2^64) in each of the n_sites (seed, offset) pairs of `table`; seeds untouched.  The
+ *   launch that moves a captured step's masks on between replays.                                                       */
+int vitpe_branch_drop_fwd(int dtype, const void* x, const void* resid, void* y, int B, long long per,
+                          const unsigned long long* rng_elem, float p_elem, const unsigned long long* rng_path,
+                          float p_path, vitpe_stream_t stream);
+int vitpe_branch_drop_bwd(int dtype, const void* dy, void* dx, int B, long long per, const unsigned long long* rng_elem,
+                          float p_elem, const unsigned long long* rng_path, float p_path, vitpe_stream_t stream);
+int vitpe_rng_advance(unsigned long long* table, int n_sites, unsigned long long inc, vitpe_stream_t stream);
 /* vitpe_attention_core_fwd_drop / _bwd_drop: vitpe_attention_core_fwd / _bwd with the reference's attention-probability
  * dropout (models/vit.py:84-88: softmax -> attn_drop -> @ v) applied to P in registers, site 2 above.  The backward
  * regenerates the mask in both of its passes: dV from P . m / (1-p), dP = (dO V^T) . m / (1-p).  p == 0 launches exactly

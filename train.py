@@ -61,6 +61,9 @@ def get_args(argv=None):
     parser.add_argument('--drop', type=float, default=0.0, help='dropout rate behind attn.proj and inside the MLP')
     parser.add_argument('--attn_drop', type=float, default=0.0, help='dropout rate on the attention probabilities')
     parser.add_argument('--drop_path', type=float, default=0.0, help='stochastic depth: rate of the last block')
+    parser.add_argument('--engine_extras', action='store_true',
+                        help='run the TrainEngine on its per-Linear route, which has the four options above (opt-in: slower '
+                             'than the fused default route)')
     args = parser.parse_args(argv)
     for name in ('drop', 'attn_drop', 'drop_path'):
         if not 0.0 <= getattr(args, name) < 1.0:
@@ -215,11 +218,12 @@ def engine_refusal(args):
     training without what was asked for.  -> message, or None."""
     active = [f for f, on in (('--qkv_bias', args.qkv_bias), ('--drop', args.drop > 0), ('--attn_drop', args.attn_drop > 0),
                               ('--drop_path', args.drop_path > 0)) if on]
-    if not active:
+    if not active or args.engine_extras:
         return None
     return ("train.py: " + ", ".join(active) + " not supported by the TrainEngine training loop (no qkv bias, no dropout in "
             "its fused kernels); models.vit.VisionTransformer(..., qkv_bias=, drop_rate=, attn_drop_rate=, drop_path_rate=) "
-            "runs them through the module path (torch autograd over torch.ops.vitpe.*)")
+            "runs them through the module path (torch autograd over torch.ops.vitpe.*).  --engine_extras trains them on the "
+            "engine's per-Linear route")
 
 
 def main(argv=None):
@@ -257,9 +261,11 @@ def main(argv=None):
     model = VisionTransformer(img_size=args.img_size, patch_size=args.patch_size, in_chans=info['in_chans'],
                               num_classes=info['num_classes'], embed_dim=args.embed_dim, depth=args.depth,
                               num_heads=args.num_heads, pos_encoding=args.pos_encoding, rope_theta=args.rope_theta,
-                              poly_degree=args.poly_degree, poly_shared_heads=args.poly_shared_heads).to(device)
+                              poly_degree=args.poly_degree, poly_shared_heads=args.poly_shared_heads,
+                              qkv_bias=args.qkv_bias, drop_rate=args.drop, attn_drop_rate=args.attn_drop,
+                              drop_path_rate=args.drop_path).to(device)   # (all off unless --engine_extras: refused above)
     engine = TrainEngine(model, per_rank, compute_dtype=torch.float32 if args.fp32 else torch.bfloat16,
-                         lr=args.lr, weight_decay=args.weight_decay)
+                         lr=args.lr, weight_decay=args.weight_decay, extras=args.engine_extras)
     engine.broadcast_parameters(0)
 
     best_acc = 0

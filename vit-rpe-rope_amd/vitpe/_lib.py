@@ -28,7 +28,8 @@ class VitpeError(RuntimeError):
     pass
 
 
-_CTYPE = {"int": ctypes.c_int, "float": ctypes.c_float, "long long": ctypes.c_longlong}
+_CTYPE = {"int": ctypes.c_int, "float": ctypes.c_float, "long long": ctypes.c_longlong,
+          "unsigned long long": ctypes.c_ulonglong}
 
 
 def parse_header(path: str = HEADER_PATH):

@@ -31,6 +31,26 @@ from .vit import VisionTransformer
 
 ALIGN = 8  # elements: keeps every parameter 32-B (fp32) / 16-B (bf16 shadow) aligned
 
+# Dropout sites of one layer in TrainEngine.rng_table (extras=True): layer l owns rows SITES_PER_LAYER * l + SITE_*, one
+# (seed, offset) pair each ("Engine route")
+SITE_ATTN, SITE_PROJ, SITE_MLP1, SITE_MLP2, SITE_PATH_A, SITE_PATH_M = range(6)
+SITES_PER_LAYER = 6
+
+
+def site_row(layer: int, site: int) -> int:
+    """Row of `site` (SITE_*) of layer `layer` in the site table."""
+    return SITES_PER_LAYER * layer + site
+
+
+def shift_rng_offsets(table: torch.Tensor, rank: int) -> torch.Tensor:
+    """A copy of the [n, 2] int64 (seed, offset) table with rank << 48 added to every offset (mod 2^64; the seeds stay):
+    data-parallel ranks that drew the same pairs (same torch seed) still never share a stream.  Pure host arithmetic on
+    whatever device the table lives on."""
+    inc = (int(rank) << 48) & 0xFFFFFFFFFFFFFFFF
+    out = table.clone()
+    out[:, 1] += inc - (1 << 64) if inc >= (1 << 63) else inc   # (two's complement: int64 addition wraps like uint64)
+    return out
+
 
 def engine_unsupported(model):
     """Names of the active model options TrainEngine cannot run (qkv bias, dropout, stochastic depth); [] if none."""
@@ -49,13 +69,19 @@ def engine_unsupported(model):
 
 class TrainEngine:
     def __init__(self, model: VisionTransformer, batch_size: int, compute_dtype=torch.bfloat16, lr=1e-3,
-                 weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, process_group=None, use_graph=True, fuse_ln=None):
+                 weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, process_group=None, use_graph=True, fuse_ln=None,
+                 extras=False):
+        """extras=True: the opt-in per-Linear route (stand-alone LayerNorm, vitpe_linear, attention core, grouped weight
+        gradients) at every geometry, which runs qkv bias, dropout, attention dropout and stochastic depth; a model with
+        none of them active runs the same route (a comparator for the fused default)."""
         active = engine_unsupported(model)
-        if active:
+        if active and not extras:
             # the flat buffers and fused kernels of this engine have no bias input on the qkv projection and no dropout
             # (DESIGN.md 8): refuse instead of silently training without them
             raise NotImplementedError("TrainEngine does not support " + ", ".join(active) + " (the fused training path has "
-                                      "no qkv bias and no dropout); train this model through the module path instead")
+                                      "no qkv bias and no dropout); train this model through the module path instead.  "
+                                      "TrainEngine(..., extras=True) runs them on the per-Linear route")
+        self.extras = bool(extras)
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise L.VitpeError("TrainEngine needs the model on the HIP device (no CPU path)")
@@ -67,7 +93,7 @@ class TrainEngine:
         # LayerNorm fused into the neighbouring kernels (needs the 192-wide panel GEMM).  fuse_ln: None / True
         # = forward and backward (default), "fwd" = forward only (stand-alone LayerNorm-backward kernel),
         # False = stand-alone LayerNorm kernels everywhere.
-        ok = m.embed_dim == 192
+        ok = m.embed_dim == 192 and not self.extras
         if fuse_ln is None and "VITPE_FUSE_LN" in os.environ:   # experiment switch: fwd | all | off
             fuse_ln = {"fwd": "fwd", "all": True, "off": False}[os.environ["VITPE_FUSE_LN"]]
         self.fuse_ln = ok and fuse_ln is not False
@@ -88,7 +114,8 @@ class TrainEngine:
         self.M = self.B * self.N
         # CIFAR geometry: fused attention kernels (qkv never leaves the chip).  Other geometries (224/16, d=768, H=12:
         # N=197, hd=64): qkv Linear into a per-layer buffer + the per-(image, head) attention core.
-        self.attn_fused = K.fused_attention_supported(self.T, self.N, self.D, self.D // self.H)
+        # (extras: the qkv Linear with its bias + the attention core at every geometry; every fusion below hangs off these)
+        self.attn_fused = not self.extras and K.fused_attention_supported(self.T, self.N, self.D, self.D // self.H)
         if not self.attn_fused and not K.attention_core_supported(self.T, self.N, self.D // self.H):
             raise L.VitpeError(f"no attention kernel for N={self.N}, D={self.D}, hd={self.D // self.H}")
         self._save_hidden = True
@@ -98,7 +125,7 @@ class TrainEngine:
         # ViT-B/16 geometry (hd = 64, N = 197): qkv projection + PE + core in one kernel (csrc/attn_core.hip,
         # attn_fused64_fwd_kernel); the raw projection is still written once in training -- the core backward reads it.
         # VITPE_ATTN_FUSED64=0: vitpe_linear + vitpe_attention_core_fwd
-        self.attn_fused64 = (not self.attn_fused and os.environ.get("VITPE_ATTN_FUSED64", "1") == "1"
+        self.attn_fused64 = (not self.attn_fused and not self.extras and os.environ.get("VITPE_ATTN_FUSED64", "1") == "1"
                              and K.attention_fused64_supported(self.T, self.N, self.H, self.D // self.H))
         if not self.attn_fused:   # the LayerNorm / MLP fusions hang off the fused attention kernels' geometry
             self.fuse_ln = self.fuse_ln_bwd = False
@@ -114,6 +141,7 @@ class TrainEngine:
         self.fuse_lnbwd = self.lnbwd2 and os.environ.get("VITPE_FUSE_LNBWD", "1") == "1"
         self._build_flat(lr, weight_decay, betas, eps)
         self._build_buffers()
+        self._build_rng_table()
         # gradient exchange in two buckets so the first overlaps the lower half of the backward pass:
         # flat[bucket_off:] = layers split.. + final norm + head (complete after the "upper" backward),
         # flat[:bucket_off] = class token, patch embed, PE parameters, layers 0..split-1
@@ -317,9 +345,11 @@ class TrainEngine:
                              and self.group_wgrad and os.environ.get("VITPE_RECOMPUTE_LN", "0") == "1")
         xn = (lambda: None) if self.recompute_ln else (lambda: e(B, N, D))
         self.act = []
-        for _ in range(self.Lyr):
+        for blk in self.model.blocks:
+            # hd (extras route, Mlp dropout): the dropped hidden activation, fc2's operand in the forward and the weight gradient
             self.act.append(dict(xn1=xn(), m1=f(M), r1=f(M), a=e(B, N, D), xmid=e(B, N, D), xn2=xn(),
-                                 m2=f(M), r2=f(M), h=e(M, self.hid), u=e(M, self.hid)))
+                                 m2=f(M), r2=f(M), h=e(M, self.hid), u=e(M, self.hid),
+                                 hd=e(M, self.hid) if self.extras and blk.mlp.drop > 0. else None))
         self.logits, self.dlogits = f(B, self.Cn), f(B, self.Cn)
         self.out2 = f(2)
         self.metric_acc = torch.zeros(2, dtype=torch.float32, device=dev)  # [sum of batch-mean losses, #correct]
@@ -354,6 +384,10 @@ class TrainEngine:
         self.du_l = [e(M, self.hid) for _ in range(self.Lyr)]
         self.dqkv_l = [e(B, N, 3 * D) for _ in range(self.Lyr)]
         self.qkv_l = [] if self.attn_fused else [e(B, N, 3 * D) for _ in range(self.Lyr)]
+        # extras route: dY of fc2 / proj behind the backward of their branch's dropout + drop-path (None: the branch has neither)
+        on = lambda blk, p: self.extras and (p > 0. or blk.drop_path_p > 0.)  # noqa: E731
+        self.g2_l = [e(B, N, D) if on(blk, blk.mlp.drop) else None for blk in self.model.blocks]
+        self.g1_l = [e(B, N, D) if on(blk, blk.attn.proj_drop_p) else None for blk in self.model.blocks]
         self.dqkv, self.du = self.dqkv_l[0], self.du_l[0]          # (bench.py times the kernels on these)
         self.da_top = None
         if self.cls_rows:
@@ -386,9 +420,110 @@ class TrainEngine:
             self.pe.cos, self.pe.sin = K.rope_mixed_tables(pe.freqs.data, self.grid)
             self.pe_grads["dfreqs"] = self.Gr(pe.freqs)
 
+    # ---------------------------------------------------------------- dropout sites (extras)
+    def _build_rng_table(self):
+        """rng_table [6 * depth, 2] int64: the (seed, offset) pair of every dropout site (SITE_* order), drawn from torch's
+        device generator (torch.manual_seed reproduces a run), offsets shifted by rank << 48.  The kernels read their row
+        from device memory, and the optimizer's last launch adds 1 to every offset: a replayed graph draws new masks.
+        Not part of state_dict(): a resumed run restores it with set_rng_table()."""
+        self.rates = [(blk.attn.attn_drop_p, blk.attn.proj_drop_p, blk.mlp.drop, blk.drop_path_p) for blk in self.model.blocks]
+        self.rng_table = None
+        if not self.extras:
+            return
+        rank = dist.get_rank(self.pg) if self.world > 1 else 0
+        self.rng_table = shift_rng_offsets(K.new_rng_pairs(SITES_PER_LAYER * self.Lyr, self.dev), rank)
+        self._rng_rows = [self.rng_table[i] for i in range(self.rng_table.shape[0])]   # views: set_rng_table copies in place
+
+    def set_rng_table(self, table: torch.Tensor):
+        """Copy a [6 * depth, 2] int64 table of (seed, offset) pairs in (tests; resuming a run).  Captured graphs stay
+        valid: they read the table's memory."""
+        if self.rng_table is None:
+            raise L.VitpeError("set_rng_table: this engine was built without extras=True")
+        if table.dtype != torch.int64 or tuple(table.shape) != tuple(self.rng_table.shape):
+            raise L.VitpeError(f"set_rng_table: expected an int64 tensor of shape {tuple(self.rng_table.shape)}, got "
+                               f"{table.dtype} {tuple(table.shape)}")
+        self.rng_table.copy_(table)
+
+    def _site(self, l, site, rate):
+        """The site's row of the table, or None where its rate is 0 (nothing is launched for it)."""
+        return self._rng_rows[site_row(l, site)] if rate > 0. else None
+
+    def _branch_fwd(self, l, inp, lin, resid, out, site_e, p_e, site_p, p_p):
+        """out = resid + drop_path(dropout(lin(inp))): the residual GEMM epilogue when both rates are 0, else the Linear into
+        a scratch (dtmp: the backward's, idle during a forward) and the fused branch kernel."""
+        M, D = self.M, self.D
+        if p_e == 0. and p_p == 0.:
+            K.linear(inp, self.Sh(lin.weight), lin.bias.data, epi=L.EPI_BIAS_RESID, resid=resid.view(M, D), out=out.view(M, D))
+            return
+        K.linear(inp, self.Sh(lin.weight), lin.bias.data, out=self.dtmp.view(M, D))
+        K.branch_drop_fwd(self.dtmp, self._site(l, site_e, p_e), p_e, self._site(l, site_p, p_p), p_p, resid=resid, out=out)
+
+    def _extras_layer_fwd(self, l, train):
+        """Layer l on the per-Linear route; train: the dropout sites run at the model's rates (evaluation: none does)."""
+        blk, a, xin, M, D = self.model.blocks[l], self.act[l], self.x[l], self.M, self.D
+        p_attn, p_proj, p_mlp, p_path = self.rates[l] if train else (0., 0., 0., 0.)
+        K.layernorm_fwd(xin, blk.norm1.weight.data, blk.norm1.bias.data, blk.norm1.eps, out=a["xn1"], mean=a["m1"], rstd=a["r1"])
+        bq = blk.attn.qkv.bias
+        K.linear(a["xn1"].view(M, D), self.Sh(blk.attn.qkv.weight), None if bq is None else bq.data,
+                 out=self.qkv_l[l].view(M, 3 * D))
+        if p_attn > 0.:
+            K.attention_core_fwd_drop(self.qkv_l[l], self.H, self.pe, self._site(l, SITE_ATTN, p_attn), p_attn, out=a["a"])
+        else:
+            K.attention_core_fwd(self.qkv_l[l], self.H, self.pe, out=a["a"])
+        self._branch_fwd(l, a["a"].view(M, D), blk.attn.proj, xin, a["xmid"], SITE_PROJ, p_proj, SITE_PATH_A, p_path)
+        K.layernorm_fwd(a["xmid"], blk.norm2.weight.data, blk.norm2.bias.data, blk.norm2.eps, out=a["xn2"], mean=a["m2"],
+                        rstd=a["r2"])
+        K.linear(a["xn2"].view(M, D), self.Sh(blk.mlp.fc1.weight), blk.mlp.fc1.bias.data, epi=L.EPI_BIAS_GELU, u=a["u"],
+                 out=a["h"])
+        h = a["h"]
+        if p_mlp > 0.:   # the dropped activation is what fc2 reads, forward and weight gradient
+            h = K.dropout_fwd(a["h"], self._site(l, SITE_MLP1, p_mlp), p_mlp, out=a["hd"])
+        self._branch_fwd(l, h, blk.mlp.fc2, a["xmid"], self.x[l + 1], SITE_MLP2, p_mlp, SITE_PATH_M, p_path)
+
+    def _extras_layer_bwd(self, l):
+        """Backward of _extras_layer_fwd(l, train=True): every mask regenerated from the table's rows."""
+        blk, a, M, D, G = self.model.blocks[l], self.act[l], self.M, self.D, self.Gr
+        p_attn, p_proj, p_mlp, p_path = self.rates[l]
+        dy3, dmid3, du, dqkv = self.dx_out[l + 1], self.dx_mid[l], self.du_l[l], self.dqkv_l[l]
+        # ---- MLP branch: x_out = xmid + drop_path(drop2(fc2(drop1(gelu(fc1(LN2(xmid)))))))
+        g2 = dy3
+        if self.g2_l[l] is not None:   # fc2's dY: per layer, the grouped weight-gradient launch reads it after the chain
+            g2 = K.branch_drop_bwd(dy3, self._site(l, SITE_MLP2, p_mlp), p_mlp, self._site(l, SITE_PATH_M, p_path), p_path,
+                                   out=self.g2_l[l])
+        g2 = g2.view(M, D)
+        hx = a["hd"] if a["hd"] is not None else a["h"]
+        self._wgrad(lambda: K.gemm_tn(g2, hx, G(blk.mlp.fc2.weight), G(blk.mlp.fc2.bias)))
+        K.linear(g2, self.St(blk.mlp.fc2.weight), None, epi=L.EPI_GELU_BWD, u=a["u"], out=du)
+        if p_mlp > 0.:   # (g2 W2) . gelu'(u) . m1 / (1 - p): the two elementwise factors commute
+            K.dropout_bwd(du, self._site(l, SITE_MLP1, p_mlp), p_mlp, out=du)
+        self._wgrad(lambda: K.gemm_tn(du, a["xn2"].view(M, D), G(blk.mlp.fc1.weight), G(blk.mlp.fc1.bias)))
+        K.linear(du, self.St(blk.mlp.fc1.weight), None, out=self.dtmp.view(M, D))
+        K.layernorm_bwd(self.dtmp, a["xmid"], a["m2"], a["r2"], blk.norm2.weight.data, G(blk.norm2.weight), G(blk.norm2.bias),
+                        dres=dy3, out=dmid3, workspace=self.ln_ws)
+        # ---- attention branch: xmid = x_in + drop_path(proj_drop(proj(attn(LN1(x_in)))))
+        g1 = dmid3
+        if self.g1_l[l] is not None:
+            g1 = K.branch_drop_bwd(dmid3, self._site(l, SITE_PROJ, p_proj), p_proj, self._site(l, SITE_PATH_A, p_path), p_path,
+                                   out=self.g1_l[l])
+        g1 = g1.view(M, D)
+        self._wgrad(lambda: K.gemm_tn(g1, a["a"].view(M, D), G(blk.attn.proj.weight), G(blk.attn.proj.bias)))
+        K.linear(g1, self.St(blk.attn.proj.weight), None, out=self.dtmp.view(M, D))
+        if p_attn > 0.:
+            K.attention_core_bwd_drop(self.qkv_l[l], self.dtmp, self.H, self.pe, self._site(l, SITE_ATTN, p_attn), p_attn,
+                                      out=dqkv, **self.pe_grads)
+        else:
+            K.attention_core_bwd(self.qkv_l[l], self.dtmp, self.H, self.pe, out=dqkv, **self.pe_grads)
+        bq = blk.attn.qkv.bias
+        self._wgrad(lambda: K.gemm_tn(dqkv.view(M, 3 * D), a["xn1"].view(M, D), G(blk.attn.qkv.weight),
+                                      None if bq is None else G(bq)))
+        K.linear(dqkv.view(M, 3 * D), self.St(blk.attn.qkv.weight), None, out=self.dtmp.view(M, D))
+        K.layernorm_bwd(self.dtmp, self.x[l], a["m1"], a["r1"], blk.norm1.weight.data, G(blk.norm1.weight), G(blk.norm1.bias),
+                        dres=dmid3, out=self.dx_out[l], workspace=self.ln_ws)
+
     # ---------------------------------------------------------------- forward / backward
-    def _forward(self, head=True, save=False):
-        """save: keep what backward needs of the MLP hidden layer (training); evaluation writes none of it."""
+    def _forward(self, head=True, save=False, train=False):
+        """save: keep what backward needs of the MLP hidden layer (training); evaluation writes none of it.
+        train (extras route): run the dropout sites; an evaluation forward applies the qkv bias and no dropout."""
         self._save_hidden = save
         mdl, B, N, D, M = self.model, self.B, self.N, self.D, self.M
         ape = mdl.pos_embed.pos_embed.data[0, :self.P] if isinstance(mdl.pos_embed, AbsolutePositionalEncoding) else None
@@ -415,6 +550,9 @@ class TrainEngine:
             K.rope_mixed_tables(mdl.pos_embed.freqs.data, self.grid, self.pe.cos, self.pe.sin)
         for l, blk in enumerate(mdl.blocks):
             a, xin = self.act[l], self.x[l]
+            if self.extras:
+                self._extras_layer_fwd(l, train)
+                continue
             if self.fuse_ln:
                 # LN1 inside the attention kernel's token staging; LN2 inside fc1's operand staging; their
                 # statistics come out of the producing GEMM's epilogue (proj / previous fc2)
@@ -515,7 +653,7 @@ class TrainEngine:
         return (4 * M * D + 2 * M * hid) * es   # dy, x_mid in; d x_mid, d attn out; u in, du out
 
     def _fwd_train(self):
-        self._forward(head=not self.fuse_head, save=True)
+        self._forward(head=not self.fuse_head, save=True, train=True)
 
     def _loss(self, tick=True):
         """tick: this loss belongs to a full step -- the fused head launch also advances the optimizer's step counter."""
@@ -543,9 +681,13 @@ class TrainEngine:
                        (a["m1"], a["r1"], blk.norm1.weight.data, blk.norm1.bias.data))
             else:
                 fc1 = (self.du_l[l], a["xn2"].view(M, D), G(blk.mlp.fc1.weight), G(blk.mlp.fc1.bias))
-                qkv = (self.dqkv_l[l].view(M, 3 * D), a["xn1"].view(M, D), G(blk.attn.qkv.weight), None)
-            fc2 = (self.dx_out[l + 1].view(M, D), a["h"], G(blk.mlp.fc2.weight), G(blk.mlp.fc2.bias))
-            proj = (self.dx_mid[l].view(M, D), a["a"].view(M, D), G(blk.attn.proj.weight), G(blk.attn.proj.bias))
+                bq = blk.attn.qkv.bias   # (extras route only)
+                qkv = (self.dqkv_l[l].view(M, 3 * D), a["xn1"].view(M, D), G(blk.attn.qkv.weight), None if bq is None else G(bq))
+            # extras route: dY behind the branch's dropout / drop-path backward, X the dropped hidden activation
+            g2 = self.g2_l[l] if self.g2_l[l] is not None else self.dx_out[l + 1]
+            g1 = self.g1_l[l] if self.g1_l[l] is not None else self.dx_mid[l]
+            fc2 = (g2.view(M, D), a["hd"] if a["hd"] is not None else a["h"], G(blk.mlp.fc2.weight), G(blk.mlp.fc2.bias))
+            proj = (g1.view(M, D), a["a"].view(M, D), G(blk.attn.proj.weight), G(blk.attn.proj.bias))
             if self._top_cls(l):   # their dY is zero outside the class rows: contract over rows b * N only (row step N)
                 fc2, fc1, proj = ((p + (None,) * (5 - len(p)) + (self.N,)) for p in (fc2, fc1, proj))
             probs += [fc2, fc1, proj, qkv]
@@ -592,6 +734,9 @@ class TrainEngine:
                        G(mdl.head.weight), G(mdl.head.bias), G(mdl.norm.weight), G(mdl.norm.bias), dx=dxL,
                        ws_dyn=self.ws_dyn)
         for l in range(hi, lo - 1, -1):
+            if self.extras:
+                self._extras_layer_bwd(l)
+                continue
             blk, a = mdl.blocks[l], self.act[l]
             dy3, dmid3, du, dqkv = self.dx_out[l + 1], self.dx_mid[l], self.du_l[l], self.dqkv_l[l]
             dy = dy3.view(M, D)
@@ -651,6 +796,8 @@ class TrainEngine:
                      zero_grad=True)
         self._ticked = False
         self.refresh_shadows(cast_flat=False)
+        if self.extras:   # the step's last launch, after the backward has regenerated the forward's masks: the next step
+            K.rng_advance(self.rng_table, 1)   # (or replay) draws new ones.  Once per step in every step shape
 
     def _allreduce(self):
         if self.allpairs is not None:
@@ -686,7 +833,8 @@ class TrainEngine:
     def capture(self):
         """Warm up on a side stream, then capture forward+loss+backward (and, single-GPU, the
         optimizer) into HIP graphs.  Engine state is restored after the warm-up."""
-        snap = [t.clone() for t in (self.flat_p, self.flat_m, self.flat_v, self.hp, self.metric_acc)]
+        state = (self.flat_p, self.flat_m, self.flat_v, self.hp, self.metric_acc) + ((self.rng_table,) if self.extras else ())
+        snap = [t.clone() for t in state]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -694,7 +842,7 @@ class TrainEngine:
                 self._fwd_train(); self._loss(); self._backward(); self._optimizer()
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
-        for t, c in zip((self.flat_p, self.flat_m, self.flat_v, self.hp, self.metric_acc), snap):
+        for t, c in zip(state, snap):
             t.copy_(c)
         self.flat_g.zero_()
         self.refresh_shadows()
@@ -885,6 +1033,9 @@ class TrainEngine:
         attention with the xn side output, block tails, grouped weight gradients): bench.py rotates over the layers'
         buffers so that no launch finds its input in L2, and prices each against min(MFMA peak, HBM peak x AI).
         Gradients accumulate garbage meanwhile: callers zero flat_g afterwards."""
+        if self.extras:
+            raise NotImplementedError("kernel_probes: not available on an extras=True engine (the probes price the fused "
+                                      "default route's kernels; build the engine without extras)")
         mdl, M, D, B, N, Hh, hid = self.model, self.M, self.D, self.B, self.N, self.H, self.hid
         G, es = self.Gr, 2 if self.T == torch.bfloat16 else 4
         hd = D // Hh

@@ -593,6 +593,50 @@ def drop_path_bwd(dy, rng, p, out=None):
     return dx
 
 
+def _branch_drop_args(x, rng_elem, rng_path):
+    if rng_elem is None and rng_path is None:
+        raise L.VitpeError("branch_drop: at least one of rng_elem / rng_path must be given")
+    for rng in (rng_elem, rng_path):
+        if rng is not None:
+            _check_rng(rng)
+    B = x.shape[0]
+    return B, x.numel() // max(B, 1)
+
+
+def branch_drop_fwd(x, rng_elem, p_elem, rng_path, p_path, resid=None, out=None):
+    """y = [resid +] (x . m_e / (1 - p_elem)) * m_b / (1 - p_path) in one pass: dropout_fwd followed by drop_path_fwd, bit
+    for bit.  rng_elem / rng_path None leaves that site out; the samples are the leading dimension."""
+    require_device(x, resid, out)
+    B, per = _branch_drop_args(x, rng_elem, rng_path)
+    y = out if out is not None else torch.empty_like(x)
+    assert resid is None or (resid.shape == x.shape and resid.dtype == x.dtype)
+    assert y.dtype == x.dtype and y.numel() == x.numel()
+    check(lib().vitpe_branch_drop_fwd(dtype_code(x.dtype), ptr(x), ptr(resid), ptr(y), B, per, ptr(rng_elem), float(p_elem),
+                                      ptr(rng_path), float(p_path), stream_ptr()), "vitpe_branch_drop_fwd")
+    return y
+
+
+def branch_drop_bwd(dy, rng_elem, p_elem, rng_path, p_path, out=None):
+    """dx = dy . m_e / (1 - p_elem) * m_b / (1 - p_path) with the forward's pairs (dropout_bwd, then drop_path_bwd)."""
+    require_device(dy, out)
+    B, per = _branch_drop_args(dy, rng_elem, rng_path)
+    dx = out if out is not None else torch.empty_like(dy)
+    assert dx.dtype == dy.dtype and dx.numel() == dy.numel()
+    check(lib().vitpe_branch_drop_bwd(dtype_code(dy.dtype), ptr(dy), ptr(dx), B, per, ptr(rng_elem), float(p_elem),
+                                      ptr(rng_path), float(p_path), stream_ptr()), "vitpe_branch_drop_bwd")
+    return dx
+
+
+def rng_advance(table, inc=1):
+    """offset += inc (mod 2^64) in every (seed, offset) row of `table` [n, 2] int64, on the device (no host sync)."""
+    require_device(table)
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 2:
+        raise L.VitpeError("rng_advance: table must be a contiguous [n, 2] int64 device tensor")
+    check(lib().vitpe_rng_advance(ptr(table), table.shape[0], int(inc) & 0xFFFFFFFFFFFFFFFF, stream_ptr()),
+          "vitpe_rng_advance")
+    return table
+
+
 def attention_core_fwd_drop(qkv, num_heads, pe: PETables, rng, p, out=None):
     """attention_core_fwd with attention-probability dropout (softmax -> dropout -> @ v) inside the kernel."""
     require_device(qkv, out)
