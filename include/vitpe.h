@@ -126,6 +126,19 @@ int vitpe_attention_core_bwd(int dtype, const void* qkv, const void* dout, void*
                              int HD, int mode, const float* cos, const float* sin, const float* table,
                              const float* coeff, int grid, int degree, int coeff_per_head, float* dtable,
                              float* dcoeff, float* dfreqs, vitpe_stream_t stream);
+/* vitpe_attention_core_probs: the attention probabilities themselves -- models/vit.py:71-84, the tensor `attn` after
+ * `.softmax(dim=-1)` and before `self.attn_drop` (what a forward hook on softmax sees; never dropped out), computed from the
+ * same qkv buffer and PE operands as vitpe_attention_core_fwd, for attention maps, class-token saliency and attention
+ * distance.  No gradient.
+ *   probs  fp32 [B,H,N,N], element ((b H + h) N + i) N + j = probability of key j for query i   (cls_only == 0)
+ *          fp32 [B,H,N]  : row i = 0 only, the class token's attention over all tokens, bitwise row 0 of the above
+ *                          (cls_only != 0: one query-tile job per (image, head))
+ * 4 B H N^2 bytes (52 MB at B 512 / H 6 / N 65).  Rows are written with 16-byte stores where N % 4 == 0 and probs is
+ * 16-byte aligned, with 4-byte stores otherwise; nothing is written past query or key N - 1.  Arguments are checked and
+ * refused exactly as by vitpe_attention_core_fwd (same supported shapes, B == 0 is a no-op); no sync, no allocation.   */
+int vitpe_attention_core_probs(int dtype, const void* qkv, float* probs, int cls_only, int B, int N, int H, int HD,
+                               int mode, const float* cos, const float* sin, const float* table, const float* coeff,
+                               int grid, int degree, int coeff_per_head, vitpe_stream_t stream);
 /* vitpe_attention_core_bwd_tables: vitpe_attention_core_bwd under RoPE with the CALLER's tables (mode rope-axial: cos / sin
  * [P,HD/2]; rope-mixed: [H,P,HD/2]), which also returns their gradients -- the autograd of the reference's rotation
  * w.r.t. cos and sin as independent inputs (models/rope_utils.py:3-37, models/vit.py:51-68): per rotate-half pair

@@ -39,6 +39,7 @@ struct AttnArgs {
   const unsigned long long* rng;
   unsigned drop_thr;
   float drop_rs;
+  int cls_only;        // probabilities kernel (attn_core_probs.hip): out = probs fp32 [B,H,N,N], or [B,H,N] (row 0 only) if set
 };
 
 // ---- host side: the one argument path behind every attention entry point (attn.hip, attn32.hip, attn_core.hip) ----

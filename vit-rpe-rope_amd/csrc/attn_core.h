@@ -1,5 +1,6 @@
 // Kernel templates of the general attention core (attn_core.hip: head dimensions 32 / 64, the C ABI and the fused
-// hd-64 forward; attn_core_hd.hip: the padded head dimensions 24 / 48 and 96 / 128, one translation unit each).
+// hd-64 forward; attn_core_hd.hip: the padded head dimensions 24 / 48 and 96 / 128, one translation unit each;
+// attn_core_probs.hip: the softmax probabilities themselves, every head dimension, one translation unit each).
 #pragma once
 #include "attn_common.h"
 #include "philox.h"
@@ -800,12 +801,21 @@ constexpr bool core_fits() {
 // dimension -- csrc/Makefile's CORE_HDS names exactly these, keep the two in step; 0: instantiated in attn_core.hip.
 #define VITPE_CORE_HDS(X) X(64, 0) X(32, 0) X(24, 1) X(48, 1) X(96, 1) X(128, 1)
 
+// what a launch of the core computes: dispatch_core's `op` (attn_core.hip)
+enum { CORE_FWD = 0, CORE_BWD = 1, CORE_PROBS = 2 };
+
+// CORE_PROBS: attn_core_probs_kernel, defined and instantiated in attn_core_probs.hip (every head dimension of
+// VITPE_CORE_HDS x VITPE_CORE_MTS x {bf16, float}; csrc/Makefile's PROBS_HDS) -- everywhere else only this declaration
+template <typename T, int HD, int MT>
+__attribute__((visibility("hidden"))) int launch_core_probs(const AttnArgs& a, hipStream_t s);
+
 template <typename T, int HD>
-__attribute__((visibility("hidden"))) int dispatch_core_t(bool bwd, int MT, const AttnArgs& a, hipStream_t s) {
-#define VITPE_CORE_CASE(T_, HD_, MT_)                                                    \
-  if (MT == MT_) {                                                                       \
-    if constexpr (core_fits<T_, HD_, MT_>()) return launch_core<T_, HD_, MT_>(bwd, a, s); \
-    else return (int)hipErrorNotSupported;                                               \
+__attribute__((visibility("hidden"))) int dispatch_core_t(int op, int MT, const AttnArgs& a, hipStream_t s) {
+#define VITPE_CORE_CASE(T_, HD_, MT_)                                                                  \
+  if (MT == MT_) {                                                                                     \
+    if constexpr (core_fits<T_, HD_, MT_>())                                                           \
+      return op == CORE_PROBS ? launch_core_probs<T_, HD_, MT_>(a, s) : launch_core<T_, HD_, MT_>(op == CORE_BWD, a, s); \
+    else return (int)hipErrorNotSupported;                                                             \
   }
   VITPE_CORE_MTS(VITPE_CORE_CASE, T, HD)
 #undef VITPE_CORE_CASE
@@ -828,8 +838,8 @@ __attribute__((visibility("hidden"))) bool core_supported_t(int MT) {
 #define VITPE_CORE_HD_LINKAGE extern
 #endif
 #define VITPE_CORE_DECLARE_HD(HD)                                                                       \
-  VITPE_CORE_HD_LINKAGE template int dispatch_core_t<bf16, HD>(bool, int, const AttnArgs&, hipStream_t);  \
-  VITPE_CORE_HD_LINKAGE template int dispatch_core_t<float, HD>(bool, int, const AttnArgs&, hipStream_t); \
+  VITPE_CORE_HD_LINKAGE template int dispatch_core_t<bf16, HD>(int, int, const AttnArgs&, hipStream_t);   \
+  VITPE_CORE_HD_LINKAGE template int dispatch_core_t<float, HD>(int, int, const AttnArgs&, hipStream_t);  \
   VITPE_CORE_HD_LINKAGE template bool core_supported_t<bf16, HD>(int);                                    \
   VITPE_CORE_HD_LINKAGE template bool core_supported_t<float, HD>(int);
 #define VITPE_CORE_DECLARE_HD_0(HD)

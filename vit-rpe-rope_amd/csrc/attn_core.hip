@@ -272,10 +272,10 @@ __global__ __launch_bounds__(64 * F64_NW) void attn_fused64_fwd_kernel(AttnArgs 
 
 using namespace vitpe;
 
-static int dispatch_core(bool bwd, int dtype, int HD, const AttnArgs& a, hipStream_t s) {
+static int dispatch_core(int op, int dtype, int HD, const AttnArgs& a, hipStream_t s) {
   const int MT = (a.N + 15) / 16;
-#define VITPE_CORE_BF16_CASE(HD_, OWN_TU_) if (dtype == 1 && HD == HD_) return dispatch_core_t<bf16, HD_>(bwd, MT, a, s);
-#define VITPE_CORE_F32_CASE(HD_, OWN_TU_) if (dtype == 0 && HD == HD_) return dispatch_core_t<float, HD_>(bwd, MT, a, s);
+#define VITPE_CORE_BF16_CASE(HD_, OWN_TU_) if (dtype == 1 && HD == HD_) return dispatch_core_t<bf16, HD_>(op, MT, a, s);
+#define VITPE_CORE_F32_CASE(HD_, OWN_TU_) if (dtype == 0 && HD == HD_) return dispatch_core_t<float, HD_>(op, MT, a, s);
   VITPE_CORE_HDS(VITPE_CORE_BF16_CASE)
   VITPE_CORE_HDS(VITPE_CORE_F32_CASE)
 #undef VITPE_CORE_BF16_CASE
@@ -295,13 +295,15 @@ extern "C" int vitpe_attention_core_supported(int dtype, int N, int HD) {
   return 0;
 }
 
-// The one body behind the five core entry points.  out: the merged heads (forward) or dqkv (backward).  rng != NULL with
+// The one body behind the six core entry points.  op: CORE_FWD / CORE_BWD / CORE_PROBS.  out: the merged heads (forward),
+// dqkv (backward) or the fp32 probabilities (CORE_PROBS: [B,H,N,N], or [B,H,N] under cls_only).  rng != NULL with
 // p > 0: the dropout kernels; p == 0 launches exactly the kernels without it.  workspace != NULL
 // (vitpe_attention_core_bwd_tables): the backward also returns the gradients w.r.t. the caller's rotary tables, so the mode
 // is a rope mode and dtable / dcoeff / dfreqs are not looked at.
-static int core_entry(bool bwd, int dtype, const void* qkv, const void* dout, void* out, int B, int N, int H, int HD,
+static int core_entry(int op, int dtype, const void* qkv, const void* dout, void* out, int B, int N, int H, int HD,
                       const PeArgs& pe, float* dtable, float* dcoeff, float* dfreqs, const unsigned long long* rng, float p,
-                      float* dcos, float* dsin, float* workspace, hipStream_t stream) {
+                      float* dcos, float* dsin, float* workspace, hipStream_t stream, int cls_only = 0) {
+  const bool bwd = op == CORE_BWD;
   const bool tables = workspace != nullptr;
   VITPE_REQUIRE(qkv && (dout || !bwd) && out && B >= 0 && N >= 2 && H >= 1);
   if (tables) VITPE_REQUIRE(pe.mode == PE_ROPE_AXIAL || pe.mode == PE_ROPE_MIXED);
@@ -311,10 +313,11 @@ static int core_entry(bool bwd, int dtype, const void* qkv, const void* dout, vo
   if (B == 0) return 0;
   AttnArgs a = attn_args(pe, B, N, H, HD);
   a.qkv = qkv; a.dout = dout; a.out = out;
+  a.cls_only = cls_only != 0;
   if (tables) a.tab_slab = workspace;
   else if (bwd) { a.dtable = dtable; a.dcoeff = dcoeff; a.dfreqs = dfreqs; }
   if (rng && p > 0.0f) { a.rng = rng; a.drop_thr = drop_threshold(p); a.drop_rs = drop_scale(p); }
-  const int e = dispatch_core(bwd, dtype, HD, a, stream);
+  const int e = dispatch_core(op, dtype, HD, a, stream);
   if (e || !tables) return e;
   // every (q/k, image[, head]) wrote its contribution into a slab of the workspace: sum them in a fixed order
   const bool mixed = pe.mode == PE_ROPE_MIXED;
@@ -325,8 +328,17 @@ static int core_entry(bool bwd, int dtype, const void* qkv, const void* dout, vo
 extern "C" int vitpe_attention_core_fwd(int dtype, const void* qkv, void* out, int B, int N, int H, int HD, int mode,
                                         const float* cos, const float* sin, const float* table, const float* coeff,
                                         int grid, int degree, int coeff_per_head, hipStream_t stream) {
-  return core_entry(false, dtype, qkv, nullptr, out, B, N, H, HD, {mode, cos, sin, table, coeff, grid, degree, coeff_per_head},
+  return core_entry(CORE_FWD, dtype, qkv, nullptr, out, B, N, H, HD, {mode, cos, sin, table, coeff, grid, degree, coeff_per_head},
                     nullptr, nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr, nullptr, stream);
+}
+
+// The attention probabilities themselves (reference vit.py:71-84: `attn` after .softmax(-1), before attn_drop), fp32
+// [B,H,N,N]; cls_only: the class token's row only, [B,H,N] (attn_core_probs.hip).  Checks and refusals: the forward's.
+extern "C" int vitpe_attention_core_probs(int dtype, const void* qkv, float* probs, int cls_only, int B, int N, int H, int HD,
+                                          int mode, const float* cos, const float* sin, const float* table, const float* coeff,
+                                          int grid, int degree, int coeff_per_head, hipStream_t stream) {
+  return core_entry(CORE_PROBS, dtype, qkv, nullptr, probs, B, N, H, HD, {mode, cos, sin, table, coeff, grid, degree, coeff_per_head},
+                    nullptr, nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr, nullptr, stream, cls_only);
 }
 
 // Attention-probability dropout inside the core (reference vit.py:84-88, softmax -> attn_drop -> @ v).  p == 0 launches
@@ -336,7 +348,7 @@ extern "C" int vitpe_attention_core_fwd_drop(int dtype, const void* qkv, void* o
                                              int grid, int degree, int coeff_per_head, const unsigned long long* rng, float p,
                                              hipStream_t stream) {
   VITPE_REQUIRE(rng && drop_p_ok(p));
-  return core_entry(false, dtype, qkv, nullptr, out, B, N, H, HD, {mode, cos, sin, table, coeff, grid, degree, coeff_per_head},
+  return core_entry(CORE_FWD, dtype, qkv, nullptr, out, B, N, H, HD, {mode, cos, sin, table, coeff, grid, degree, coeff_per_head},
                     nullptr, nullptr, nullptr, rng, p, nullptr, nullptr, nullptr, stream);
 }
 
@@ -371,7 +383,7 @@ extern "C" int vitpe_attention_core_bwd(int dtype, const void* qkv, const void* 
                                         int HD, int mode, const float* cos, const float* sin, const float* table,
                                         const float* coeff, int grid, int degree, int coeff_per_head, float* dtable,
                                         float* dcoeff, float* dfreqs, hipStream_t stream) {
-  return core_entry(true, dtype, qkv, dout, dqkv, B, N, H, HD, {mode, cos, sin, table, coeff, grid, degree, coeff_per_head},
+  return core_entry(CORE_BWD, dtype, qkv, dout, dqkv, B, N, H, HD, {mode, cos, sin, table, coeff, grid, degree, coeff_per_head},
                     dtable, dcoeff, dfreqs, nullptr, 0.0f, nullptr, nullptr, nullptr, stream);
 }
 
@@ -381,7 +393,7 @@ extern "C" int vitpe_attention_core_bwd_drop(int dtype, const void* qkv, const v
                                              float* dcoeff, float* dfreqs, const unsigned long long* rng, float p,
                                              hipStream_t stream) {
   VITPE_REQUIRE(rng && drop_p_ok(p));
-  return core_entry(true, dtype, qkv, dout, dqkv, B, N, H, HD, {mode, cos, sin, table, coeff, grid, degree, coeff_per_head},
+  return core_entry(CORE_BWD, dtype, qkv, dout, dqkv, B, N, H, HD, {mode, cos, sin, table, coeff, grid, degree, coeff_per_head},
                     dtable, dcoeff, dfreqs, rng, p, nullptr, nullptr, nullptr, stream);
 }
 
@@ -395,6 +407,6 @@ extern "C" int vitpe_attention_core_bwd_tables(int dtype, const void* qkv, const
                                                float* dcoeff, float* dfreqs, float* dcos, float* dsin, float* workspace,
                                                hipStream_t stream) {
   VITPE_REQUIRE(workspace);
-  return core_entry(true, dtype, qkv, dout, dqkv, B, N, H, HD, {mode, cos, sin, table, coeff, grid, degree, coeff_per_head},
+  return core_entry(CORE_BWD, dtype, qkv, dout, dqkv, B, N, H, HD, {mode, cos, sin, table, coeff, grid, degree, coeff_per_head},
                     dtable, dcoeff, dfreqs, nullptr, 0.0f, dcos, dsin, workspace, stream);
 }

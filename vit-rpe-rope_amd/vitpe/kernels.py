@@ -475,6 +475,23 @@ def attention_core_fwd(qkv, num_heads, pe: PETables, out=None):
     return o
 
 
+def attention_core_probs(qkv, num_heads, pe: PETables, cls_only=False, out=None):
+    """qkv [B,N,3D] (output of the qkv Linear) -> the attention probabilities softmax(QK^T hd^-0.5 [+ bias]) in fp32:
+    [B,H,N,N], or with cls_only the class token's row alone, [B,H,N] (bitwise row 0 of the full result).  The tensor the
+    reference calls `attn` between softmax and attn_drop (vit.py:71-84), from the same operands as attention_core_fwd; never
+    dropped out, no gradient."""
+    require_device(qkv, out, pe.cos, pe.sin, pe.table, pe.coeff)
+    B, N, D3 = qkv.shape
+    HD = D3 // 3 // num_heads
+    shape = (B, num_heads, N) if cls_only else (B, num_heads, N, N)
+    o = out if out is not None else torch.empty(shape, dtype=torch.float32, device=qkv.device)
+    if tuple(o.shape) != shape or o.dtype != torch.float32:
+        raise L.VitpeError(f"attention_core_probs: out must be float32 {shape}")
+    check(lib().vitpe_attention_core_probs(dtype_code(qkv.dtype), ptr(qkv), ptr(o), int(bool(cls_only)), B, N, num_heads, HD,
+                                           *_pe_tail(pe), stream_ptr()), "vitpe_attention_core_probs")
+    return o
+
+
 def attention_fused64_supported(dtype, N, num_heads, HD) -> bool:
     return bool(lib().vitpe_attention_fused64_supported(dtype_code(dtype), int(N), int(num_heads), int(HD)))
 

@@ -250,6 +250,24 @@ def _attn_drop_backward(ctx, dy, _da, _dqkv):
 attention_drop.register_autograd(_attn_drop_backward, setup_context=_attn_drop_setup)
 
 
+# ---- attention probabilities (reference vit.py:71-84: `attn` after softmax, before attn_drop) -------------------------------
+@torch.library.custom_op("vitpe::attention_probs", mutates_args=())
+def attention_probs(qkv: Tensor, num_heads: int, mode: int, grid: int, pe_param: Optional[Tensor], inv_freq: Optional[Tensor],
+                    degree: int, per_head: bool, cos: Optional[Tensor] = None, sin: Optional[Tensor] = None,
+                    cls_only: bool = False) -> Tensor:
+    """qkv [B,N,3D] (the qkv Linear's output) -> softmax(QK^T hd^-0.5 [+ bias]) fp32 [B,H,N,N]; cls_only: the class token's
+    row, [B,H,N].  PE arguments as vitpe::attention.  For analysis: no autograd is registered, the result is a constant."""
+    t = _pe_tables(mode, grid, pe_param, inv_freq, degree, per_head, cos, sin)
+    return K.attention_core_probs(qkv.contiguous(), num_heads, t, cls_only=cls_only)
+
+
+@attention_probs.register_fake
+def _(qkv, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos=None, sin=None, cls_only=False):
+    B, N, _ = qkv.shape
+    shape = (B, num_heads, N) if cls_only else (B, num_heads, N, N)
+    return qkv.new_empty(shape, dtype=torch.float32)
+
+
 # ---- mlp: y = [resid +] fc2(gelu(fc1(xn)))  (timm Mlp, reference vit.py:118,124) ----------------
 @torch.library.custom_op("vitpe::mlp", mutates_args=())
 def mlp(xn: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, resid: Optional[Tensor], p: float = 0.0,

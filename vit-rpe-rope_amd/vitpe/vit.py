@@ -92,14 +92,13 @@ class Attention(nn.Module):
         self.proj_drop = nn.Dropout(proj_drop)
         self.pos_encoding = None
 
-    def forward(self, x, freqs_cis=None, resid=None):
-        require_device(x)
-        B, N, C = x.shape
+    def _pe_operands(self, N, freqs_cis):
+        """(mode, pe_param, inv_freq, degree, per_head, cos, sin, tables_grad): the positional-encoding arguments of the
+        attention ops for N tokens and the caller's freqs_cis."""
         # RoPE rotates only when the caller passes freqs_cis (reference vit.py:51).  VisionTransformer.forward_features
         # passes a marker and the kernel builds the tables on the device from the module's own parameters (which keeps
         # the RoPE-mixed frequencies trainable); a caller's own (cos, sin) tensors are used AS GIVEN (vit.py:51-64).
         mode, pe_param, inv_freq, degree, per_head = _pe_args(self.pos_encoding, freqs_cis is not None)
-        grid = int(math.sqrt(N - 1))
         cos = sin = None
         tables_grad = False
         if isinstance(freqs_cis, (tuple, list)) and len(freqs_cis) == 2 and all(torch.is_tensor(t) for t in freqs_cis):
@@ -121,6 +120,13 @@ class Attention(nn.Module):
                 # qkv Linear + core route, whose backward returns d cos / d sin (vitpe::attention, tables_grad)
                 tables_grad = torch.is_grad_enabled() and (cos.requires_grad or sin.requires_grad)
                 mode, pe_param, inv_freq = (_MODE["rope-axial"] if cos.dim() == 2 else _MODE["rope-mixed"]), None, None
+        return mode, pe_param, inv_freq, degree, per_head, cos, sin, tables_grad
+
+    def forward(self, x, freqs_cis=None, resid=None):
+        require_device(x)
+        B, N, C = x.shape
+        mode, pe_param, inv_freq, degree, per_head, cos, sin, tables_grad = self._pe_operands(N, freqs_cis)
+        grid = int(math.sqrt(N - 1))
         attn_p = self.attn_drop_p if self.training else 0.
         proj_p = self.proj_drop_p if self.training else 0.
         self.last_rng = None   # (set below if this forward draws pairs)
@@ -138,6 +144,24 @@ class Attention(nn.Module):
                                               self.num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos, sin,
                                               tables_grad, attn_p, proj_p, rng)
         return y
+
+    def attention_probs(self, x, freqs_cis=None, cls_only=False):
+        """The attention probabilities of forward(x, freqs_cis): softmax(QK^T hd^-0.5 [+ bias]), the reference's `attn`
+        after .softmax(dim=-1) and before attn_drop (vit.py:71-84) -- what a forward hook on its softmax would catch.
+        x: the same input as forward's (the tokens after norm1); freqs_cis: the same marker or (cos, sin) tables.
+        -> fp32 [B, H, N, N]; cls_only: the class token's row alone, [B, H, N].
+
+        Always the undropped softmax, whatever self.training and attn_drop are; no RNG is drawn; the result carries no
+        gradient.  The route is the qkv Linear (with qkv.bias if the module has one) + the probabilities kernel of the
+        attention core at every geometry -- also at those where forward runs a one-kernel fused path (N 65 / hd 32,
+        N 197 / hd 64), which keep the probabilities on the chip."""
+        require_device(x)
+        B, N, C = x.shape
+        with torch.no_grad():
+            mode, pe_param, inv_freq, degree, per_head, cos, sin, _ = self._pe_operands(N, freqs_cis)
+            qkv = K.linear(x.contiguous().view(B * N, C), ops._shadow(self.qkv.weight, x.dtype), self.qkv.bias).view(B, N, 3 * C)
+            return torch.ops.vitpe.attention_probs(qkv, self.num_heads, mode, int(math.sqrt(N - 1)), pe_param, inv_freq,
+                                                   degree, per_head, cos, sin, bool(cls_only))
 
     def _own_mixed_tables(self, cos, sin):
         """Are (cos, sin) provably RoPEMixed.get_freqs_cis of this module's own `freqs` (one _MixedTables node whose
@@ -184,6 +208,12 @@ class Block(nn.Module):
         x = self.attn(n1, freqs_cis=freqs_cis, resid=x)      # x + attn(norm1(x)), residual fused in the proj GEMM
         n2 = torch.ops.vitpe.layer_norm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps)[0]
         return self.mlp(n2, resid=x)                          # x + mlp(norm2(x)), residual fused in the fc2 GEMM
+
+    def attention_probs(self, x, freqs_cis=None, cls_only=False):
+        """The attention probabilities of this block's forward(x, freqs_cis): Attention.attention_probs on norm1(x)."""
+        with torch.no_grad():
+            n1 = torch.ops.vitpe.layer_norm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)[0]
+        return self.attn.attention_probs(n1, freqs_cis=freqs_cis, cls_only=cls_only)
 
     def set_pos_encoding(self, pos_encoding):
         self.attn.set_pos_encoding(pos_encoding)
@@ -283,6 +313,39 @@ class VisionTransformer(nn.Module):
         for blk in self.blocks:
             x = blk(x, freqs_cis=freqs_cis)
         return x
+
+    def attention_maps(self, x, layers=None, cls_only=False):
+        """{layer: attention probabilities} of the eval forward of images x [B,C,H,W]: fp32 [B, H, N, N] per requested layer
+        (default: every block), or [B, H, N] -- the class token's row -- with cls_only.  4 B H N^2 bytes a layer.
+
+        Runs forward_features' own sequence under torch.no_grad() with eval semantics (no dropout, no stochastic depth, no
+        RNG drawn; the training flags are restored afterwards): the tokens entering block l + 1 are the ordinary eval
+        forward's, the probabilities of block l come from Block.attention_probs on its input."""
+        require_device(x)
+        depth = len(self.blocks)
+        want = list(range(depth)) if layers is None else sorted({int(l) for l in layers})
+        if want and not (0 <= want[0] and want[-1] < depth):
+            raise ValueError(f"vitpe attention_maps: layers must be in [0, {depth}), got {list(layers)}")
+        last = want[-1] if want else -1
+        flags = [(m, m.training) for m in self.modules()]
+        self.eval()
+        try:
+            with torch.no_grad():
+                B, C, H, W = x.shape
+                ape = self.pos_embed.pos_embed if self.use_pos_embed_in_forward else None
+                t = torch.ops.vitpe.patch_embed(x, self.patch_embed.weight, self.patch_embed.bias, self.cls_token, ape,
+                                                self.patch_size, self.compute_dtype == torch.bfloat16)[0]
+                freqs_cis = ((H // self.patch_size) * (W // self.patch_size),) if self.use_rope else None
+                maps = {}
+                for l, blk in enumerate(self.blocks[:last + 1]):
+                    if l in want:
+                        maps[l] = blk.attention_probs(t, freqs_cis=freqs_cis, cls_only=cls_only)
+                    if l < last:
+                        t = blk(t, freqs_cis=freqs_cis)
+                return maps
+        finally:
+            for m, was in flags:
+                m.training = was
 
     def forward(self, x):
         """logits [B,num_classes] fp32 (reference vit.py:273-285); the final LayerNorm is only
