@@ -414,6 +414,29 @@ int vitpe_patch_embed(int dtype, const float* img, const unsigned char* data, co
                       const float* nmean, const float* nstd, const void* W, const float* bias, const float* cls,
                       const float* ape, void* tokens, void* patches, float* mean, float* rstd, int B, int C, int S,
                       int p, int D, float eps, vitpe_stream_t stream);
+/* Augmentation stream: transforms.RandomCrop(S, padding=pad) + transforms.RandomHorizontalFlip() between the Resize and the
+ * ToTensor of the reference's input pipeline (train.py:69-92, which has neither), applied inside the two gather kernels
+ * above.  `rng` is a DEVICE pointer to the site's two 64-bit words (seed, offset), as for a dropout site.  Batch slot b (the
+ * position in the batch, not the record) makes ONE Philox4x32-10 call,
+ *   key = (lo32 seed, hi32 seed) ; counter = (lo32 b, hi32 b, lo32 offset, hi32 offset) -> words w0..w3
+ *   oy = mulhi32(w0, 2 pad + 1) ; ox = mulhi32(w1, 2 pad + 1) ; flip = hflip && (w2 >> 31)
+ * and its output pixel (c, y, x) is the source byte u = data[index[b], c, y + oy - pad, (flip ? S-1-x : x) + ox - pad], or
+ * u = 0 outside the image (zero padding of the uint8 image), then ((float)u / 255 - mean[c]) / std[c] as above.
+ * 0 <= pad <= S, else hipErrorInvalidValue.  rng == NULL, or pad == 0 with hflip == 0: the unaugmented result, bit for bit.
+ * vitpe_unfold_u8_aug  : vitpe_unfold_u8 + (rng, pad, hflip); img_out receives the augmented image.
+ * vitpe_patch_embed_aug: vitpe_patch_embed + (rng, pad, hflip), on the `data` path only: img != NULL with rng != NULL is
+ *   hipErrorInvalidValue; at p == 4 with rng != NULL `data` must be 4-byte aligned (the rows are read as aligned dwords).
+ * vitpe_augment_params : the draws themselves, out [B,3] int = (oy, ox, flip) of slots 0..B-1, for tests.
+ * vitpe_rng_advance moves the pair on between steps.                                                                  */
+int vitpe_unfold_u8_aug(int dtype, const unsigned char* data, const long long* index, const float* mean,
+                        const float* stdv, void* patches, float* img_out, int B, int C, int S, int p,
+                        const unsigned long long* rng, int pad, int hflip, vitpe_stream_t stream);
+int vitpe_patch_embed_aug(int dtype, const float* img, const unsigned char* data, const long long* index,
+                          const float* nmean, const float* nstd, const void* W, const float* bias, const float* cls,
+                          const float* ape, void* tokens, void* patches, float* mean, float* rstd, int B, int C, int S,
+                          int p, int D, float eps, const unsigned long long* rng, int pad, int hflip,
+                          vitpe_stream_t stream);
+int vitpe_augment_params(const unsigned long long* rng, int* out, int B, int pad, int hflip, vitpe_stream_t stream);
 /* dcls[d] += sum_b dtok[b,0,d]; dape[p,d] += sum_b dtok[b,1+p,d] (NULL to skip);
  * dpatch [B*P,D] T = patch rows of dtok (input of the patch-embed weight gradient)            */
 int vitpe_embed_bwd(int dtype, const void* dtok, float* dcls, float* dape, void* dpatch, int B,

@@ -11,7 +11,8 @@ all-reduce of the flat gradient bucket per step.
 
 Additions to the reference CLI: --synthetic (CIFAR/MNIST-shaped random batches generated on the
 device: torchvision and the dataset downloads are unavailable offline), --steps_per_epoch,
---fp32 (exact-fp32 MFMA instead of the default bf16).  --batch_size is the GLOBAL batch.
+--fp32 (exact-fp32 MFMA instead of the default bf16), --random_crop PAD / --hflip (RandomCrop(img_size, padding=PAD) /
+RandomHorizontalFlip on the training images, drawn inside the embed kernel).  --batch_size is the GLOBAL batch.
 """
 import argparse
 import csv
@@ -64,7 +65,13 @@ def get_args(argv=None):
     parser.add_argument('--engine_extras', action='store_true',
                         help='run the TrainEngine on its per-Linear route, which has the four options above (opt-in: slower '
                              'than the fused default route)')
+    # input augmentation of the training loop (the reference's pipeline has none); evaluation never augments
+    parser.add_argument('--random_crop', type=int, default=0, metavar='PAD',
+                        help='RandomCrop(img_size, padding=PAD) on the training images (0 = off)')
+    parser.add_argument('--hflip', action='store_true', help='RandomHorizontalFlip() on the training images')
     args = parser.parse_args(argv)
+    if not 0 <= args.random_crop <= args.img_size:
+        parser.error(f"--random_crop must be in 0..--img_size ({args.img_size})")
     for name in ('drop', 'attn_drop', 'drop_path'):
         if not 0.0 <= getattr(args, name) < 1.0:
             parser.error(f"--{name} must be in [0, 1)")
@@ -226,9 +233,20 @@ def engine_refusal(args):
             "engine's per-Linear route")
 
 
+def augment_refusal(args):
+    """The crop and the flip are drawn inside the gather from the resident uint8 dataset; --synthetic has none.
+    -> message, or None."""
+    active = [f for f, on in (('--random_crop', args.random_crop > 0), ('--hflip', args.hflip)) if on]
+    if not active or not args.synthetic:
+        return None
+    return ("train.py: " + ", ".join(active) + " cannot be combined with --synthetic: the augmentation runs inside the "
+            "embed kernel's gather from the dataset resident in HBM, and the synthetic batches are fp32 tensors with no "
+            "such dataset behind them; drop --synthetic (see --data_dir) or the augmentation flags")
+
+
 def main(argv=None):
     args = get_args(argv)
-    extras = engine_refusal(args)
+    extras = engine_refusal(args) or augment_refusal(args)
     if extras:   # up front: before the dataset is loaded and the device touched
         raise SystemExit(extras)
     if not torch.cuda.is_available():
@@ -267,6 +285,8 @@ def main(argv=None):
     engine = TrainEngine(model, per_rank, compute_dtype=torch.float32 if args.fp32 else torch.bfloat16,
                          lr=args.lr, weight_decay=args.weight_decay, extras=args.engine_extras)
     engine.broadcast_parameters(0)
+    if args.random_crop > 0 or args.hflip:   # training steps only: test() runs forward_indexed, which never augments
+        engine.set_augment(args.random_crop, args.hflip)
 
     best_acc = 0
     for epoch in range(args.epochs):

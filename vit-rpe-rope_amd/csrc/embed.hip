@@ -12,7 +12,13 @@
 // The product runs on the matrix core (4 token tiles x D/16 feature tiles x K/32 chunks); bias / PE add, the row
 // statistics and the stores happen on the accumulators (a lane owns four consecutive features of one token per tile).
 // Replaces three launches (vitpe_unfold[_u8] + vitpe_gemm_nt(EPI_PATCH) + vitpe_layernorm_fwd statistics).
+//
+// AUG (vitpe_patch_embed_aug, uint8 path only): the gather also applies the augmentation stream of augment.h -- one draw per
+// workgroup (= image), the crop and the flip are address arithmetic of the same loads.  The p == 4 row of a cropped patch
+// is unaligned and may straddle the image border: it is cut out of the two ALIGNED dwords of the source row that cover it
+// (a dword outside the row is the constant 0 == the zero padding), byte-reversed under a flip.
 #include "common.h"
+#include "augment.h"
 
 namespace vitpe {
 
@@ -32,6 +38,8 @@ struct EmbedArgs {
   float* rstd;
   int B, C, S, p, D;
   float eps;
+  const unsigned long long* rng;   // AUG only: the site's (seed, offset) pair; crop padding; flip enabled
+  int pad, hflip;
 };
 
 constexpr int EMB_KP = 64;     // padded K
@@ -42,7 +50,7 @@ constexpr int EMB_DMAX = 256;
 // orientation (A = weight rows, B = patch rows): acc[nt][r] = out[token 16w + c][feature 16nt + 4g + r], so a lane holds
 // four consecutive features of ONE token per tile: the row statistics are an in-lane sum over the tiles plus a
 // cross-group (g) reduction with two permlane swaps, and the stores are 8 B per lane -- no fp32 staging of the result.
-template <typename T>
+template <typename T, bool AUG>
 __global__ __launch_bounds__(256) void patch_embed_kernel(EmbedArgs a) {
   constexpr int LDA = EMB_KP + 2 * Pad<T>::elems;    // operand rows: 10 (bf16) slots, == 2 mod 4: conflict-free fragment reads
   constexpr int CHN = CH<T>::n, NTMAX = EMB_DMAX / 16, KSM = EMB_KP / 32;
@@ -73,6 +81,8 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(EmbedArgs a) {
   }
   const long long rec = a.data != nullptr ? (a.index != nullptr ? a.index[b] : (long long)b) : 0;
   T* pout = a.patches != nullptr ? reinterpret_cast<T*>(a.patches) + (size_t)b * P * K : nullptr;
+  AugDraw aug = {0, 0, 0};
+  if (AUG) aug = aug_draw(a.rng, (unsigned long long)b, a.pad, a.hflip);   // uniform over the workgroup
   for (int q = tid; q < P * C * p; q += 256) {           // (patch n, channel, row ky): p contiguous pixels
     const int ky = q % p, ch = (q / p) % C, n = q / (p * C);
     const int gy = n / G, gx = n % G;
@@ -80,7 +90,21 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(EmbedArgs a) {
     const int k0 = ch * p * p + ky * p;
     if (p == 4) {   // the CIFAR / MNIST patch: one 16-B (fp32) or 4-B (uint8) load, one 8-B / 16-B store each way
       float v[4];
-      if (a.data != nullptr) {
+      if (AUG) {
+        const int sy = gy * p + ky + aug.oy - a.pad;
+        const int lo = (aug.flip ? S - 4 - gx * p : gx * p) + aug.ox - a.pad;   // leftmost source column of the four
+        const int d0 = lo >> 2, sh = 8 * (lo & 3);                              // (floor / non-negative remainder)
+        const bool rowok = sy >= 0 && sy < S;                                   // (S % 4 == 0: a dword never straddles the row end)
+        const uint32_t* row =
+            reinterpret_cast<const uint32_t*>(a.data + (size_t)rec * C * S * S + ((size_t)ch * S + (rowok ? sy : 0)) * S);
+        const uint32_t w0 = rowok && d0 >= 0 && 4 * d0 < S ? row[d0] : 0u;
+        const uint32_t w1 = rowok && d0 + 1 >= 0 && 4 * (d0 + 1) < S ? row[d0 + 1] : 0u;
+        uint32_t u = (uint32_t)((((uint64_t)w1 << 32) | w0) >> sh);
+        if (aug.flip) u = __builtin_bswap32(u);
+        const float m = a.nmean[ch], sd = a.nstd[ch];
+        v[0] = ((float)(u & 0xffu) / 255.0f - m) / sd; v[1] = ((float)((u >> 8) & 0xffu) / 255.0f - m) / sd;
+        v[2] = ((float)((u >> 16) & 0xffu) / 255.0f - m) / sd; v[3] = ((float)(u >> 24) / 255.0f - m) / sd;
+      } else if (a.data != nullptr) {
         const uchar4 u = *reinterpret_cast<const uchar4*>(a.data + (size_t)rec * C * S * S + pix);
         const float m = a.nmean[ch], sd = a.nstd[ch];   // ToTensor then Normalize, IEEE division (as vitpe_unfold_u8)
         v[0] = ((float)u.x / 255.0f - m) / sd; v[1] = ((float)u.y / 255.0f - m) / sd;
@@ -94,7 +118,14 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(EmbedArgs a) {
     } else {
       for (int kx = 0; kx < p; ++kx) {
         float v;
-        if (a.data != nullptr)
+        if (AUG) {
+          const int sy = gy * p + ky + aug.oy - a.pad;
+          const int sx = (aug.flip ? S - 1 - (gx * p + kx) : gx * p + kx) + aug.ox - a.pad;
+          const bool in = sy >= 0 && sy < S && sx >= 0 && sx < S;
+          unsigned char u = 0;   // the zero padding
+          if (in) u = a.data[(size_t)rec * C * S * S + ((size_t)ch * S + sy) * S + sx];
+          v = ((float)u / 255.0f - a.nmean[ch]) / a.nstd[ch];
+        } else if (a.data != nullptr)
           v = ((float)a.data[(size_t)rec * C * S * S + pix + kx] / 255.0f - a.nmean[ch]) / a.nstd[ch];
         else
           v = a.img[(size_t)b * C * S * S + pix + kx];
@@ -200,21 +231,47 @@ extern "C" int vitpe_patch_embed_supported(int dtype, int C, int S, int p, int D
   return K <= EMB_KP && K % (dtype == 1 ? 8 : 4) == 0 && P <= EMB_MP && D >= 16 && D <= EMB_DMAX && D % 16 == 0;
 }
 
-// img XOR data: fp32 images [B,C,S,S], or the resident uint8 dataset + sample indices (as vitpe_unfold_u8).
-extern "C" int vitpe_patch_embed(int dtype, const float* img, const unsigned char* data, const long long* index,
-                                 const float* nmean, const float* nstd, const void* W, const float* bias, const float* cls,
-                                 const float* ape, void* tokens, void* patches, float* mean, float* rstd, int B, int C, int S,
-                                 int p, int D, float eps, hipStream_t stream) {
+static int launch_patch_embed(int dtype, const float* img, const unsigned char* data, const long long* index,
+                              const float* nmean, const float* nstd, const void* W, const float* bias, const float* cls,
+                              const float* ape, void* tokens, void* patches, float* mean, float* rstd, int B, int C, int S,
+                              int p, int D, float eps, const unsigned long long* rng, int pad, int hflip, hipStream_t stream) {
   VITPE_REQUIRE(W && bias && cls && tokens && B >= 0);
   VITPE_REQUIRE((img != nullptr) != (data != nullptr));
   VITPE_REQUIRE(data == nullptr || (nmean && nstd));
   VITPE_REQUIRE((mean == nullptr) == (rstd == nullptr));
+  VITPE_REQUIRE(rng == nullptr || (img == nullptr && pad >= 0 && pad <= S));
+  VITPE_REQUIRE(rng == nullptr || p != 4 || ((uintptr_t)data & 3) == 0);   // the aligned dwords of the p == 4 rows
   if (!vitpe_patch_embed_supported(dtype, C, S, p, D)) return (int)hipErrorNotSupported;
   if (B == 0) return 0;
   EmbedArgs a{};
   a.img = img; a.data = data; a.index = index; a.nmean = nmean; a.nstd = nstd; a.W = W; a.bias = bias; a.cls = cls; a.ape = ape;
   a.tokens = tokens; a.patches = patches; a.mean = mean; a.rstd = rstd; a.B = B; a.C = C; a.S = S; a.p = p; a.D = D; a.eps = eps;
-  if (dtype == 1) hipLaunchKernelGGL(patch_embed_kernel<bf16>, dim3(B), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL(patch_embed_kernel<float>, dim3(B), dim3(256), 0, stream, a);
+  a.rng = rng; a.pad = pad; a.hflip = hflip;
+  if (rng != nullptr) {
+    if (dtype == 1) hipLaunchKernelGGL((patch_embed_kernel<bf16, true>), dim3(B), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((patch_embed_kernel<float, true>), dim3(B), dim3(256), 0, stream, a);
+  } else {
+    if (dtype == 1) hipLaunchKernelGGL((patch_embed_kernel<bf16, false>), dim3(B), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((patch_embed_kernel<float, false>), dim3(B), dim3(256), 0, stream, a);
+  }
   VITPE_CHECK_LAUNCH();
+}
+
+// img XOR data: fp32 images [B,C,S,S], or the resident uint8 dataset + sample indices (as vitpe_unfold_u8).
+extern "C" int vitpe_patch_embed(int dtype, const float* img, const unsigned char* data, const long long* index,
+                                 const float* nmean, const float* nstd, const void* W, const float* bias, const float* cls,
+                                 const float* ape, void* tokens, void* patches, float* mean, float* rstd, int B, int C, int S,
+                                 int p, int D, float eps, hipStream_t stream) {
+  return launch_patch_embed(dtype, img, data, index, nmean, nstd, W, bias, cls, ape, tokens, patches, mean, rstd, B, C, S, p, D,
+                            eps, nullptr, 0, 0, stream);
+}
+
+// the same with the augmentation stream on the uint8 path (rng NULL: exactly vitpe_patch_embed)
+extern "C" int vitpe_patch_embed_aug(int dtype, const float* img, const unsigned char* data, const long long* index,
+                                     const float* nmean, const float* nstd, const void* W, const float* bias,
+                                     const float* cls, const float* ape, void* tokens, void* patches, float* mean,
+                                     float* rstd, int B, int C, int S, int p, int D, float eps, const unsigned long long* rng,
+                                     int pad, int hflip, hipStream_t stream) {
+  return launch_patch_embed(dtype, img, data, index, nmean, nstd, W, bias, cls, ape, tokens, patches, mean, rstd, B, C, S, p, D,
+                            eps, rng, pad, hflip, stream);
 }

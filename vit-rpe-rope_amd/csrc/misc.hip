@@ -1,6 +1,7 @@
 // Patch-embed unfold, positional-encoding table builders, stand-alone rotary apply, classifier
 // head + cross-entropy, fused AdamW with weight shadows, and the primitive self-tests.
 #include "common.h"
+#include "augment.h"
 
 namespace vitpe {
 
@@ -51,12 +52,17 @@ __global__ void unfold8_kernel(const float* __restrict__ img, bf16* __restrict__
 // ToTensor (x/255) -> Normalize((x-mean)/std) -> model): record index[b] of data [Ndata,C,S,S] (the
 // CIFAR-10 binary / MNIST idx pixel order) is normalised in fp32 with the reference's operation
 // order and written straight as the patch matrix; img_out (nullable) receives the fp32 image.
-template <typename T>
+// AUG (vitpe_unfold_u8_aug): the source pixel goes through the augmentation stream of augment.h (random crop with zero
+// padding + horizontal flip per batch slot b); the draw is repeated only when a thread moves on to another image.
+template <typename T, bool AUG>
 __global__ void unfold_u8_kernel(const unsigned char* __restrict__ data, const long long* __restrict__ index,
                                  const float* __restrict__ mean, const float* __restrict__ stdv, T* __restrict__ patches,
-                                 float* __restrict__ img_out, int B, int Cc, int S, int p) {
+                                 float* __restrict__ img_out, int B, int Cc, int S, int p,
+                                 const unsigned long long* __restrict__ rng, int pad, int hflip) {
   const int g = S / p, P = g * g, Kp = Cc * p * p;
   const long long total = (long long)B * P * Cc * p;
+  AugDraw aug = {0, 0, 0};
+  int aug_b = -1;
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
        idx += (long long)gridDim.x * blockDim.x) {
     const int ky = (int)(idx % p);
@@ -70,12 +76,36 @@ __global__ void unfold_u8_kernel(const unsigned char* __restrict__ data, const l
     const unsigned char* src = data + (size_t)rec * Cc * S * S + pix;
     T* dst = patches + ((size_t)b * P + n) * Kp + ch * p * p + ky * p;
     const float m = mean[ch], sd = stdv[ch];
+    if (AUG) {
+      if (b != aug_b) { aug = aug_draw(rng, (unsigned long long)b, pad, hflip); aug_b = b; }
+      const int sy = gy * p + ky + aug.oy - pad;
+      const bool rowok = sy >= 0 && sy < S;
+      const unsigned char* row = data + (size_t)rec * Cc * S * S + ((size_t)ch * S + (rowok ? sy : 0)) * S;
+      for (int kx = 0; kx < p; ++kx) {
+        const int sx = (aug.flip ? S - 1 - (gx * p + kx) : gx * p + kx) + aug.ox - pad;
+        unsigned char u = 0;   // the zero padding
+        if (rowok && sx >= 0 && sx < S) u = row[sx];
+        const float v = ((float)u / 255.0f - m) / sd;
+        dst[kx] = from_f32<T>(v);
+        if (img_out != nullptr) img_out[(size_t)b * Cc * S * S + pix + kx] = v;
+      }
+      continue;
+    }
     for (int kx = 0; kx < p; ++kx) {
       const float v = ((float)src[kx] / 255.0f - m) / sd;   // ToTensor then Normalize, IEEE division
       dst[kx] = from_f32<T>(v);
       if (img_out != nullptr) img_out[(size_t)b * Cc * S * S + pix + kx] = v;
     }
   }
+}
+
+// the draws of the first B batch slots as integers (tests): out [B,3] = (oy, ox, flip)
+__global__ void augment_params_kernel(const unsigned long long* __restrict__ rng, int* __restrict__ out, int B, int pad,
+                                      int hflip) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const AugDraw d = aug_draw(rng, (unsigned long long)b, pad, hflip);
+  out[3 * b] = d.oy; out[3 * b + 1] = d.ox; out[3 * b + 2] = d.flip;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -832,17 +862,45 @@ extern "C" int vitpe_unfold(int dtype, const float* img, void* patches, int B, i
   VITPE_CHECK_LAUNCH();
 }
 
-extern "C" int vitpe_unfold_u8(int dtype, const unsigned char* data, const long long* index, const float* mean,
-                               const float* stdv, void* patches, float* img_out, int B, int C, int S, int p,
-                               hipStream_t st) {
+static int launch_unfold_u8(int dtype, const unsigned char* data, const long long* index, const float* mean,
+                            const float* stdv, void* patches, float* img_out, int B, int C, int S, int p,
+                            const unsigned long long* rng, int pad, int hflip, hipStream_t st) {
   VITPE_REQUIRE(data && mean && stdv && patches && B >= 0 && C > 0 && p > 0 && S % p == 0 && (dtype == 0 || dtype == 1));
+  VITPE_REQUIRE(rng == nullptr || (pad >= 0 && pad <= S));
   const long long total = (long long)B * (S / p) * (S / p) * C * p;
   if (total == 0) return 0;
   const unsigned blocks = (unsigned)min((total + 255) / 256, (long long)8192);
-  if (dtype == 1)
-    hipLaunchKernelGGL(unfold_u8_kernel<bf16>, dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (bf16*)patches, img_out, B, C, S, p);
-  else
-    hipLaunchKernelGGL(unfold_u8_kernel<float>, dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (float*)patches, img_out, B, C, S, p);
+  if (rng != nullptr) {
+    if (dtype == 1)
+      hipLaunchKernelGGL((unfold_u8_kernel<bf16, true>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (bf16*)patches, img_out, B, C, S, p, rng, pad, hflip);
+    else
+      hipLaunchKernelGGL((unfold_u8_kernel<float, true>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (float*)patches, img_out, B, C, S, p, rng, pad, hflip);
+  } else {
+    if (dtype == 1)
+      hipLaunchKernelGGL((unfold_u8_kernel<bf16, false>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (bf16*)patches, img_out, B, C, S, p, rng, 0, 0);
+    else
+      hipLaunchKernelGGL((unfold_u8_kernel<float, false>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (float*)patches, img_out, B, C, S, p, rng, 0, 0);
+  }
+  VITPE_CHECK_LAUNCH();
+}
+
+extern "C" int vitpe_unfold_u8(int dtype, const unsigned char* data, const long long* index, const float* mean,
+                               const float* stdv, void* patches, float* img_out, int B, int C, int S, int p,
+                               hipStream_t st) {
+  return launch_unfold_u8(dtype, data, index, mean, stdv, patches, img_out, B, C, S, p, nullptr, 0, 0, st);
+}
+
+// the same with the augmentation stream (rng NULL: exactly vitpe_unfold_u8)
+extern "C" int vitpe_unfold_u8_aug(int dtype, const unsigned char* data, const long long* index, const float* mean,
+                                   const float* stdv, void* patches, float* img_out, int B, int C, int S, int p,
+                                   const unsigned long long* rng, int pad, int hflip, hipStream_t st) {
+  return launch_unfold_u8(dtype, data, index, mean, stdv, patches, img_out, B, C, S, p, rng, pad, hflip, st);
+}
+
+extern "C" int vitpe_augment_params(const unsigned long long* rng, int* out, int B, int pad, int hflip, hipStream_t st) {
+  VITPE_REQUIRE(rng && B >= 0 && (out || B == 0) && pad >= 0);
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(augment_params_kernel, GRID1D(B), 0, st, rng, out, B, pad, hflip);
   VITPE_CHECK_LAUNCH();
 }
 

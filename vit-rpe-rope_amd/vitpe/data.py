@@ -171,3 +171,21 @@ def epoch_global_batches(n_items: int, global_batch: int, epoch: int, seed: int 
             yield order[k0 + lo:k0 + hi], hi - lo, n_global
         else:
             yield order[k0:k0 + 1], 0, n_global
+
+
+def augment_batch(dataset: ResidentDataset, idx: Optional[torch.Tensor], rng: torch.Tensor, crop_pad: int = 0,
+                  hflip: bool = False) -> torch.Tensor:
+    """Normalised, augmented images fp32 [B,C,S,S] of samples `idx` (int64 [B] on the device; None: the first records) for
+    the module path (`model(images)`): RandomCrop(S, padding=crop_pad) + RandomHorizontalFlip (if hflip) between Resize
+    and ToTensor, on the augmentation stream of the pair `rng` ("Augmentation stream") -- the pixels the
+    engine's embed kernels see for the same pair.  One launch (kernels.unfold_u8's img_out); advance the pair between
+    batches with kernels.rng_advance."""
+    from . import kernels as K
+    K._check_augment(rng, crop_pad, dataset.images.shape[2], "augment_batch")
+    _, C, S, _ = dataset.images.shape
+    B = idx.shape[0] if idx is not None else dataset.images.shape[0]
+    images = torch.empty((B, C, S, S), dtype=torch.float32, device=dataset.device)
+    with torch.cuda.device(dataset.device):   # (one patch per image: the patch matrix is the image itself, a scratch here)
+        K.unfold_u8(dataset.images, idx, dataset.mean, dataset.std, S, torch.float32, img_out=images, rng=rng,
+                    crop_pad=crop_pad, hflip=hflip)
+    return images

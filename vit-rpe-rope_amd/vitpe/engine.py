@@ -52,6 +52,13 @@ def shift_rng_offsets(table: torch.Tensor, rank: int) -> torch.Tensor:
     return out
 
 
+def new_augment_rng(device, rank: int = 0) -> torch.Tensor:
+    """The (seed, offset) pair [1, 2] int64 of the augmentation stream ("Augmentation stream"): drawn from
+    torch's generator of `device` (torch.manual_seed reproduces it), the offset shifted by rank << 48 like the dropout
+    sites' -- data-parallel ranks never crop alike."""
+    return shift_rng_offsets(K.new_rng_pairs(1, device), rank)
+
+
 def engine_unsupported(model):
     """Names of the active model options TrainEngine cannot run (qkv bias, dropout, stochastic depth); [] if none."""
     active = []
@@ -142,6 +149,7 @@ class TrainEngine:
         self._build_flat(lr, weight_decay, betas, eps)
         self._build_buffers()
         self._build_rng_table()
+        self.aug_rng, self.aug_pad, self.aug_hflip = None, 0, False   # set_augment()
         # gradient exchange in two buckets so the first overlaps the lower half of the backward pass:
         # flat[bucket_off:] = layers split.. + final norm + head (complete after the "upper" backward),
         # flat[:bucket_off] = class token, patch embed, PE parameters, layers 0..split-1
@@ -444,6 +452,27 @@ class TrainEngine:
                                f"{table.dtype} {tuple(table.shape)}")
         self.rng_table.copy_(table)
 
+    def set_augment(self, crop_pad: int = 0, hflip: bool = False, rng: Optional[torch.Tensor] = None):
+        """RandomCrop(S, padding=crop_pad) + RandomHorizontalFlip (if hflip) on the training steps' input, inside the embed
+        kernel's gather from the resident dataset ("Augmentation stream"); evaluation forwards never augment.
+        `engine.aug_rng` [1, 2] int64 is the stream's (seed, offset) pair: drawn from torch's device generator with the
+        offset shifted by rank << 48, or a copy of `rng` (two int64 words on the device) as it is; every optimizer step
+        advances the offset by 1.  Not part of state_dict() (as rng_table).  The defaults switch augmentation off.
+        Captured graphs are dropped."""
+        crop_pad, hflip = int(crop_pad), bool(hflip)
+        if not 0 <= crop_pad <= self.S:
+            raise L.VitpeError(f"set_augment: crop_pad must be in 0..{self.S} (the image size), got {crop_pad}")
+        if rng is not None:
+            K._check_augment(rng, crop_pad, self.S, "set_augment")
+        if crop_pad == 0 and not hflip:
+            self.aug_rng = None
+        elif rng is not None:
+            self.aug_rng = rng.to(self.dev).reshape(1, 2).clone()
+        else:
+            self.aug_rng = new_augment_rng(self.dev, dist.get_rank(self.pg) if self.world > 1 else 0)
+        self.aug_pad, self.aug_hflip = crop_pad, hflip
+        self.graph_fb = self.graph_fb2 = self.graph_opt = None
+
     def _site(self, l, site, rate):
         """The site's row of the table, or None where its rate is 0 (nothing is launched for it)."""
         return self._rng_rows[site_row(l, site)] if rate > 0. else None
@@ -523,12 +552,18 @@ class TrainEngine:
     # ---------------------------------------------------------------- forward / backward
     def _forward(self, head=True, save=False, train=False):
         """save: keep what backward needs of the MLP hidden layer (training); evaluation writes none of it.
-        train (extras route): run the dropout sites; an evaluation forward applies the qkv bias and no dropout."""
+        train (extras route): run the dropout sites; an evaluation forward applies the qkv bias and no dropout.
+        train (any route): the uint8 gather crops and flips on the augmentation stream when set_augment() switched it on."""
         self._save_hidden = save
         mdl, B, N, D, M = self.model, self.B, self.N, self.D, self.M
         ape = mdl.pos_embed.pos_embed.data[0, :self.P] if isinstance(mdl.pos_embed, AbsolutePositionalEncoding) else None
+        aug = {}
+        if train and self.aug_rng is not None:
+            if self.dataset is None:
+                raise L.VitpeError(self._AUG_NEEDS_DATASET)
+            aug = dict(rng=self.aug_rng, crop_pad=self.aug_pad, hflip=self.aug_hflip)
         if self.fuse_embed:   # unfold + patch GEMM + bias + APE + class token + block 0's norm1 statistics: one kernel
-            src = (dict(data=self.dataset.images, index=self.batch_idx, mean=self.dataset.mean, std=self.dataset.std)
+            src = (dict(data=self.dataset.images, index=self.batch_idx, mean=self.dataset.mean, std=self.dataset.std, **aug)
                    if self.dataset is not None else dict(images=self.images))
             b0 = mdl.blocks[0]
             K.patch_embed(self.Sh(mdl.patch_embed.weight).view(D, -1), mdl.patch_embed.bias.data, mdl.cls_token.data.view(-1),
@@ -537,7 +572,7 @@ class TrainEngine:
         else:
             if self.dataset is not None:   # resident uint8 dataset: gather + ToTensor + Normalize inside the unfold
                 K.unfold_u8(self.dataset.images, self.batch_idx, self.dataset.mean, self.dataset.std, self.p, self.T,
-                            out=self.patches)
+                            out=self.patches, **aug)
             else:
                 K.unfold(self.images, self.p, self.T, out=self.patches)
             K.patch_embed_gemm(self.patches, self.Sh(mdl.patch_embed.weight).view(D, -1), mdl.patch_embed.bias.data,
@@ -651,6 +686,10 @@ class TrainEngine:
         if fwd:   # attention output + x in; x_mid, x_out (and LN2(x_mid) unless recomputed) out; u and h out (2 x [M,hid])
             return ((4 if self.recompute_ln else 5) * M * D + 2 * M * hid) * es
         return (4 * M * D + 2 * M * hid) * es   # dy, x_mid in; d x_mid, d attn out; u in, du out
+
+    _AUG_NEEDS_DATASET = ("augmentation is on (set_augment) but no resident dataset is attached: the crop and the flip run "
+                          "inside the gather from the uint8 dataset -- attach_dataset() + step_indexed(), or augment the "
+                          "images yourself with vitpe.data.augment_batch and switch it off (set_augment())")
 
     def _fwd_train(self):
         self._forward(head=not self.fuse_head, save=True, train=True)
@@ -798,6 +837,8 @@ class TrainEngine:
         self.refresh_shadows(cast_flat=False)
         if self.extras:   # the step's last launch, after the backward has regenerated the forward's masks: the next step
             K.rng_advance(self.rng_table, 1)   # (or replay) draws new ones.  Once per step in every step shape
+        if self.aug_rng is not None:   # likewise the augmentation stream: the next step crops and flips anew
+            K.rng_advance(self.aug_rng, 1)
 
     def _allreduce(self):
         if self.allpairs is not None:
@@ -834,6 +875,7 @@ class TrainEngine:
         """Warm up on a side stream, then capture forward+loss+backward (and, single-GPU, the
         optimizer) into HIP graphs.  Engine state is restored after the warm-up."""
         state = (self.flat_p, self.flat_m, self.flat_v, self.hp, self.metric_acc) + ((self.rng_table,) if self.extras else ())
+        state += (self.aug_rng,) if self.aug_rng is not None else ()
         snap = [t.clone() for t in state]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -973,6 +1015,8 @@ class TrainEngine:
         n <= B (a ragged last batch is padded and masked, see set_valid); None re-uses the resident batch.  No host
         synchronisation.  `exchange=False` skips the gradient all-reduce (measurement of the exposed communication
         time only: the replicas diverge)."""
+        if self.aug_rng is not None and self.dataset is None:   # never train silently without the crop
+            raise L.VitpeError(self._AUG_NEEDS_DATASET)
         if images is not None:
             if self.dataset is not None:
                 raise L.VitpeError("a resident dataset is attached: use step_indexed (or attach_dataset(None))")

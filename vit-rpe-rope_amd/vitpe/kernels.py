@@ -692,9 +692,32 @@ def unfold(images, patch, dtype, out=None):
     return o
 
 
-def unfold_u8(data, index, mean, std, patch, dtype, out=None, img_out=None):
+def _check_augment(rng, crop_pad, S, what):
+    """Arguments of the augmentation stream ("Augmentation stream"), checked before anything touches a device."""
+    if not isinstance(rng, torch.Tensor) or rng.dtype != torch.int64 or rng.numel() != 2:
+        raise L.VitpeError(f"{what}: rng must be a contiguous int64 device tensor of two words (seed, offset)")
+    if int(crop_pad) < 0 or (S is not None and int(crop_pad) > int(S)):
+        raise L.VitpeError(f"{what}: crop_pad must be in 0..S (the image size{'' if S is None else f', {int(S)}'}), got {crop_pad}")
+    require_device(rng)
+
+
+def augment_params(rng, B, crop_pad=0, hflip=False):
+    """int32 [B, 3] = (oy, ox, flip) of batch slots 0..B-1 for the pair `rng` (tests only: the product kernels make the
+    same draw in registers)."""
+    _check_augment(rng, crop_pad, None, "augment_params")
+    out = torch.empty((B, 3), dtype=torch.int32, device=rng.device)
+    check(lib().vitpe_augment_params(ptr(rng), ptr(out), B, int(crop_pad), int(bool(hflip)), stream_ptr()),
+          "vitpe_augment_params")
+    return out
+
+
+def unfold_u8(data, index, mean, std, patch, dtype, out=None, img_out=None, rng=None, crop_pad=0, hflip=False):
     """Resident uint8 dataset [Ndata,C,S,S] + sample indices [B] int64 (None: the first rows) -> normalised
-    patch matrix [B*P, C*p*p] (ToTensor + Normalize + unfold in one pass); img_out optionally gets the fp32 images."""
+    patch matrix [B*P, C*p*p] (ToTensor + Normalize + unfold in one pass); img_out optionally gets the fp32 images.
+    rng (a (seed, offset) pair): RandomCrop(S, padding=crop_pad) + RandomHorizontalFlip (if hflip) per batch slot, on the
+    augmentation stream, inside the same kernel; crop_pad / hflip are ignored without it."""
+    if rng is not None:
+        _check_augment(rng, crop_pad, data.shape[2], "unfold_u8")
     require_device(data, index, mean, std, out, img_out)
     if data.dtype != torch.uint8 or (index is not None and index.dtype != torch.int64):
         raise L.VitpeError("unfold_u8: data must be uint8 and index int64")
@@ -703,6 +726,11 @@ def unfold_u8(data, index, mean, std, patch, dtype, out=None, img_out=None):
     B = index.shape[0] if index is not None else data.shape[0]
     g = S // patch
     o = out if out is not None else torch.empty((B * g * g, C * patch * patch), dtype=dtype, device=data.device)
+    if rng is not None:
+        check(lib().vitpe_unfold_u8_aug(dtype_code(dtype), ptr(data), ptr(index), ptr(mean), ptr(std), ptr(o), ptr(img_out), B,
+                                        C, S, patch, ptr(rng), int(crop_pad), int(bool(hflip)), stream_ptr()),
+              "vitpe_unfold_u8_aug")
+        return o
     check(lib().vitpe_unfold_u8(dtype_code(dtype), ptr(data), ptr(index), ptr(mean), ptr(std), ptr(o), ptr(img_out), B, C, S,
                                 patch, stream_ptr()), "vitpe_unfold_u8")
     return o
@@ -756,9 +784,15 @@ def patch_embed_supported(dtype, C, S, p, D) -> bool:
 
 
 def patch_embed(w, bias, cls, ape, patch, dtype, images=None, data=None, index=None, mean=None, std=None, out=None,
-                patches_out=None, stats=None, eps=1e-5):
+                patches_out=None, stats=None, eps=1e-5, rng=None, crop_pad=0, hflip=False):
     """Fused unfold + patch-embed GEMM + bias + APE + class token (+ LayerNorm statistics of the token rows).
-    images [B,C,S,S] fp32, or data (uint8 dataset) + index [B] int64 + mean/std [C].  w [D, C*p*p] in `dtype`."""
+    images [B,C,S,S] fp32, or data (uint8 dataset) + index [B] int64 + mean/std [C].  w [D, C*p*p] in `dtype`.
+    rng (data path only): the augmentation stream, as unfold_u8."""
+    if rng is not None:
+        if images is not None or data is None:
+            raise L.VitpeError("patch_embed: rng (augmentation) needs the uint8 `data` path; augment fp32 images with "
+                               "data.augment_batch first")
+        _check_augment(rng, crop_pad, data.shape[2], "patch_embed")
     require_device(w, bias, cls, ape, images, data, index, mean, std, out, patches_out)
     src = images if images is not None else data
     C, S = src.shape[1], src.shape[2]
@@ -770,6 +804,12 @@ def patch_embed(w, bias, cls, ape, patch, dtype, images=None, data=None, index=N
     o = out if out is not None else torch.empty((B, P + 1, D), dtype=dtype, device=w.device)
     mo, ro = stats if stats is not None else (None, None)
     require_device(mo, ro)
+    if rng is not None:
+        check(lib().vitpe_patch_embed_aug(dtype_code(dtype), ptr(images), ptr(data), ptr(index), ptr(mean), ptr(std), ptr(w),
+                                          ptr(bias), ptr(cls), ptr(ape), ptr(o), ptr(patches_out), ptr(mo), ptr(ro), B, C, S,
+                                          patch, D, float(eps), ptr(rng), int(crop_pad), int(bool(hflip)), stream_ptr()),
+              "vitpe_patch_embed_aug")
+        return o
     check(lib().vitpe_patch_embed(dtype_code(dtype), ptr(images), ptr(data), ptr(index), ptr(mean), ptr(std), ptr(w), ptr(bias),
                                   ptr(cls), ptr(ape), ptr(o), ptr(patches_out), ptr(mo), ptr(ro), B, C, S, patch, D, float(eps),
                                   stream_ptr()), "vitpe_patch_embed")
