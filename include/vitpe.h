@@ -514,11 +514,28 @@ int vitpe_head_step(int dtype, const void* x, const float* gamma, const float* b
 
 /* ---- optimizer + weight shadows (train.py:116,195) ------------------------------------------
  * hp (device, 16 floats): [0]=lr [1]=beta1 [2]=beta2 [3]=eps [4]=weight_decay [5]=step
- * [6]=bias_correction1 [7]=bias_correction2 [8]=grad_scale.  The step counter lives on the
+ * [6]=bias_correction1 [7]=bias_correction2 [8]=grad_scale [9]=effective grad scale (grad_scale * clip_coef)
+ * [10]=total_norm [11]=clip_coef [12]=max_norm ([9..11] are written by vitpe_grad_clip, [12] by the host; [13..15]
+ * unused).  The step counter lives on the
  * device so the call can be replayed from a hipGraph.  zero_grad: bit 0 = clear g after the update,
- * bit 1 = the step counter / bias corrections were already advanced (vitpe_head_step hp_tick).   */
+ * bit 1 = the step counter / bias corrections were already advanced (vitpe_head_step hp_tick),
+ * bit 2 = the gradient is scaled by hp[9] instead of hp[8] (after vitpe_grad_clip).  Values 0..3 never read hp[9].  */
 int vitpe_adamw_step(float* p, float* g, float* m, float* v, void* shadow_bf16, float* hp,
                      long long n, int zero_grad, vitpe_stream_t stream);
+/* torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2.0, error_if_nonfinite=False) on the flat gradient g [n]
+ * (4-byte aligned; any offset inside a 16-byte line), as two launches without atomics and without a host read:
+ *   hp[10] = total_norm = hp[8] * sqrt(sum g[i]^2)      (the norm of the gradient AdamW uses, g * grad_scale)
+ *   hp[11] = clip_coef  = min(1, hp[12] / (total_norm + 1e-6))
+ *   hp[9]  = hp[8] * clip_coef                          (fp32 product: clip_coef == 1 gives hp[9] == hp[8] bit for bit)
+ * g itself is not changed: vitpe_adamw_step with zero_grad bit 2 scales by hp[9].  Non-finite values follow the formula
+ * (a NaN norm gives a NaN coefficient, as torch's clamp does).  partial: work buffer of n_partial >=
+ * vitpe_grad_clip_blocks(n) floats, one per workgroup of the first launch, summed in fp64 in a fixed order by the
+ * second.  The grid depends on n alone, so the result is the same bit for bit from run to run and from device to device.
+ * n == 0 (g and partial may be NULL): norm 0, coef 1.  hipErrorInvalidValue for NULL hp, NULL g / partial with n > 0,
+ * n < 0, a g that is not 4-byte aligned, or n_partial too small; nothing is launched then.                          */
+int vitpe_grad_clip(const float* g, long long n, float* hp, float* partial, int n_partial, vitpe_stream_t stream);
+/* workgroups (= floats of `partial`) vitpe_grad_clip uses for n elements: min(1024, ceil(n / 4096)); 0 for n <= 0 */
+int vitpe_grad_clip_blocks(long long n);
 int vitpe_cast(int dtype, const float* src, void* dst, long long n, vitpe_stream_t stream);
 int vitpe_transpose_cast(int dtype, const float* src, void* dst, int R, int C, vitpe_stream_t stream);
 /* every weight shadow of the model in one launch.  desc: device array of ndesc records

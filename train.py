@@ -12,7 +12,9 @@ all-reduce of the flat gradient bucket per step.
 Additions to the reference CLI: --synthetic (CIFAR/MNIST-shaped random batches generated on the
 device: torchvision and the dataset downloads are unavailable offline), --steps_per_epoch,
 --fp32 (exact-fp32 MFMA instead of the default bf16), --random_crop PAD / --hflip (RandomCrop(img_size, padding=PAD) /
-RandomHorizontalFlip on the training images, drawn inside the embed kernel).  --batch_size is the GLOBAL batch.
+RandomHorizontalFlip on the training images, drawn inside the embed kernel), --clip_grad MAX_NORM
+(torch.nn.utils.clip_grad_norm_ between backward and the optimizer step, inside the captured step).  --batch_size is the
+GLOBAL batch.
 """
 import argparse
 import csv
@@ -69,7 +71,11 @@ def get_args(argv=None):
     parser.add_argument('--random_crop', type=int, default=0, metavar='PAD',
                         help='RandomCrop(img_size, padding=PAD) on the training images (0 = off)')
     parser.add_argument('--hflip', action='store_true', help='RandomHorizontalFlip() on the training images')
+    parser.add_argument('--clip_grad', type=float, default=0.0, metavar='MAX_NORM',
+                        help='clip_grad_norm_(model.parameters(), MAX_NORM) before every optimizer step (0 = off)')
     args = parser.parse_args(argv)
+    if not (math.isfinite(args.clip_grad) and args.clip_grad >= 0.0):
+        parser.error("--clip_grad must be a finite number >= 0")
     if not 0 <= args.random_crop <= args.img_size:
         parser.error(f"--random_crop must be in 0..--img_size ({args.img_size})")
     for name in ('drop', 'attn_drop', 'drop_path'):
@@ -287,6 +293,7 @@ def main(argv=None):
     engine.broadcast_parameters(0)
     if args.random_crop > 0 or args.hflip:   # training steps only: test() runs forward_indexed, which never augments
         engine.set_augment(args.random_crop, args.hflip)
+    engine.set_grad_clip(args.clip_grad)   # 0 = off
 
     best_acc = 0
     for epoch in range(args.epochs):

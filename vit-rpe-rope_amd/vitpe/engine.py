@@ -334,6 +334,37 @@ class TrainEngine:
     def set_lr(self, lr: float):
         self.hp[0] = lr
 
+    clip_max_norm: Optional[float] = None   # set_grad_clip(); None = clipping off
+    _clip_partial = None                    # grad_clip's work buffer, allocated on the first enable
+
+    def set_grad_clip(self, max_norm: Optional[float]):
+        """torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) between the backward (after every all-reduce) and
+        AdamW, inside the step: the norm of the gradient AdamW uses (flat_g * hp[8], all parameters, L2) is reduced on the
+        device and the update scales the gradient by hp[8] * min(1, max_norm / (norm + 1e-6)) ("Gradient
+        clipping").  None or 0 switches it off (the default).  Configuration like the learning rate: not part of
+        state_dict().  Switching on or off drops the captured graphs; a new value for an enabled clip is one device
+        write (hp[12]) and keeps them.  Negative or non-finite values raise VitpeError."""
+        value = 0.0 if max_norm is None else float(max_norm)
+        if not math.isfinite(value) or value < 0.0:
+            raise L.VitpeError(f"set_grad_clip: max_norm must be None or a finite number >= 0, got {max_norm!r}")
+        new = value if value > 0.0 else None
+        if new is not None:
+            if self._clip_partial is None:
+                self._clip_partial = torch.zeros(K.grad_clip_blocks(self.n_flat), dtype=torch.float32, device=self.dev)
+            self.hp[12] = new
+        if (new is None) != (self.clip_max_norm is None):
+            self.graph_fb = self.graph_fb2 = self.graph_opt = None
+        self.clip_max_norm = new
+
+    def grad_norm(self) -> float:
+        """total_norm of the last optimizer step, before clipping (what clip_grad_norm_ returns), read from hp[10];
+        synchronises with the device.  Only defined while clipping is on (nothing computes the norm otherwise):
+        VitpeError when it is off."""
+        if self.clip_max_norm is None:
+            raise L.VitpeError("grad_norm: gradient clipping is off (set_grad_clip(max_norm) first); the norm is only "
+                               "computed as part of the clip")
+        return float(self.hp[10].item())
+
     # ---------------------------------------------------------------- activations
     def _build_buffers(self):
         B, N, D, M, T, dev = self.B, self.N, self.D, self.M, self.T, self.dev
@@ -831,8 +862,11 @@ class TrainEngine:
             self._wgrad_group(part)
 
     def _optimizer(self):
+        clip = self.clip_max_norm is not None
+        if clip:   # after every all-reduce in every step shape: all ranks reduce the same flat_g to the same coefficient
+            K.grad_clip(self.flat_g, self.hp, self._clip_partial)
         K.adamw_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.hp, shadow_bf16=self.flat_s, ticked=getattr(self, "_ticked", False),
-                     zero_grad=True)
+                     zero_grad=True, clipped=clip)
         self._ticked = False
         self.refresh_shadows(cast_flat=False)
         if self.extras:   # the step's last launch, after the backward has regenerated the forward's masks: the next step

@@ -1030,12 +1030,29 @@ def head_step(x, gamma, beta, wh, bh, labels, logits, dlogits, ws, ws_dyn, dx, o
 
 
 # ---- optimizer / shadows --------------------------------------------------------------------
-def adamw_step(p, g, m, v, hp, shadow_bf16=None, zero_grad=True, ticked=False):
-    """ticked: the step counter / bias corrections in hp were already advanced (head_step hp_tick)."""
+def adamw_step(p, g, m, v, hp, shadow_bf16=None, zero_grad=True, ticked=False, clipped=False):
+    """ticked: the step counter / bias corrections in hp were already advanced (head_step hp_tick).
+    clipped: scale the gradient by hp[9] (what grad_clip left there) instead of hp[8]."""
     require_device(p, g, m, v, hp, shadow_bf16)
     check(lib().vitpe_adamw_step(ptr(p), ptr(g), ptr(m), ptr(v), ptr(shadow_bf16), ptr(hp), p.numel(),
-                                 int(bool(zero_grad)) | (2 if ticked else 0),
+                                 int(bool(zero_grad)) | (2 if ticked else 0) | (4 if clipped else 0),
                                  stream_ptr()), "vitpe_adamw_step")
+
+
+def grad_clip_blocks(n: int) -> int:
+    """Floats of the work buffer grad_clip needs for a gradient of n elements."""
+    return lib().vitpe_grad_clip_blocks(int(n))
+
+
+def grad_clip(g, hp, partial):
+    """clip_grad_norm_ on the flat fp32 gradient g (a 1-d view at any element offset), on the device: hp[10] =
+    hp[8] * ||g||, hp[11] = min(1, hp[12] / (hp[10] + 1e-6)), hp[9] = hp[8] * hp[11] (include/vitpe.h); g is left as it
+    is -- adamw_step(clipped=True) applies hp[9].  partial: fp32 work buffer of >= grad_clip_blocks(g.numel()) floats."""
+    require_device(g, hp, partial)
+    _f32(g, "g"); _f32(hp, "hp"); _f32(partial, "partial")
+    if hp.numel() < 16:
+        raise L.VitpeError(f"grad_clip: hp must hold 16 floats, got {hp.numel()}")
+    check(lib().vitpe_grad_clip(ptr(g), g.numel(), ptr(hp), ptr(partial), partial.numel(), stream_ptr()), "vitpe_grad_clip")
 
 
 def cast(src, dtype, out=None):
