@@ -14,10 +14,12 @@
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import os
 from typing import Dict, List, Optional
 
+import numpy as np
 import torch
 import torch.distributed as dist
 import torch.nn as nn
@@ -27,9 +29,9 @@ from . import ddp
 from . import kernels as K
 from .positional_encoding import (AbsolutePositionalEncoding, PolynomialRPE, RelativePositionalEncoding, RoPEAxial,
                                   RoPEMixed)
+from .route import (ALIGN, KIND_FRAG, KIND_FRAG_PHI, KIND_QKV, KIND_QKV_WIDE, KIND_T, Route, resolve_route,  # noqa: F401
+                    shadow_plan)
 from .vit import VisionTransformer
-
-ALIGN = 8  # elements: keeps every parameter 32-B (fp32) / 16-B (bf16 shadow) aligned
 
 # Dropout sites of one layer in TrainEngine.rng_table (extras=True): layer l owns rows SITES_PER_LAYER * l + SITE_*, one
 # (seed, offset) pair each ("Engine route")
@@ -75,6 +77,10 @@ def engine_unsupported(model):
 
 
 class TrainEngine:
+    # defaults of the two attributes set_grad_clip() / grad_norm() read, so that they answer on an object that never ran
+    # __init__ (tests/test_grad_clip_cpu.py checks their argument handling without a device); __init__ sets both
+    clip_max_norm = _clip_partial = None
+
     def __init__(self, model: VisionTransformer, batch_size: int, compute_dtype=torch.bfloat16, lr=1e-3,
                  weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, process_group=None, use_graph=True, fuse_ln=None,
                  extras=False):
@@ -88,7 +94,6 @@ class TrainEngine:
             raise NotImplementedError("TrainEngine does not support " + ", ".join(active) + " (the fused training path has "
                                       "no qkv bias and no dropout); train this model through the module path instead.  "
                                       "TrainEngine(..., extras=True) runs them on the per-Linear route")
-        self.extras = bool(extras)
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise L.VitpeError("TrainEngine needs the model on the HIP device (no CPU path)")
@@ -97,55 +102,20 @@ class TrainEngine:
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         self.use_graph = use_graph
         m = model
-        # LayerNorm fused into the neighbouring kernels (needs the 192-wide panel GEMM).  fuse_ln: None / True
-        # = forward and backward (default), "fwd" = forward only (stand-alone LayerNorm-backward kernel),
-        # False = stand-alone LayerNorm kernels everywhere.
-        ok = m.embed_dim == 192 and not self.extras
-        if fuse_ln is None and "VITPE_FUSE_LN" in os.environ:   # experiment switch: fwd | all | off
-            fuse_ln = {"fwd": "fwd", "all": True, "off": False}[os.environ["VITPE_FUSE_LN"]]
-        self.fuse_ln = ok and fuse_ln is not False
-        self.fuse_ln_bwd = ok and (fuse_ln is True or fuse_ln is None)
-        self.D, self.H, self.Lyr = m.embed_dim, m.num_heads, len(m.blocks)
-        self.p = m.patch_size
-        self.C = m.patch_embed.weight.shape[1]
-
-        self.P = m.num_patches
-        self.N = self.P + 1
-        self.grid = int(math.sqrt(self.P))
-        self.S = self.grid * self.p
-        # unfold + patch GEMM + bias + APE + class token + first LayerNorm statistics in one kernel (small-K geometries)
-        self.fuse_embed = (os.environ.get("VITPE_FUSE_EMBED", "1") == "1" and
-                           K.patch_embed_supported(compute_dtype, self.C, self.S, self.p, self.D))
+        self.D, self.H, self.Lyr, self.p = m.embed_dim, m.num_heads, len(m.blocks), m.patch_size
+        self.C, self.P, self.Cn = m.patch_embed.weight.shape[1], m.num_patches, m.num_classes
+        self.N, self.grid = self.P + 1, int(math.sqrt(self.P))
+        self.S, self.M = self.grid * self.p, self.B * self.N
         self.hid = m.blocks[0].mlp.fc1.weight.shape[0]
-        self.Cn = m.num_classes
-        self.M = self.B * self.N
-        # CIFAR geometry: fused attention kernels (qkv never leaves the chip).  Other geometries (224/16, d=768, H=12:
-        # N=197, hd=64): qkv Linear into a per-layer buffer + the per-(image, head) attention core.
-        # (extras: the qkv Linear with its bias + the attention core at every geometry; every fusion below hangs off these)
-        self.attn_fused = not self.extras and K.fused_attention_supported(self.T, self.N, self.D, self.D // self.H)
-        if not self.attn_fused and not K.attention_core_supported(self.T, self.N, self.D // self.H):
-            raise L.VitpeError(f"no attention kernel for N={self.N}, D={self.D}, hd={self.D // self.H}")
+        # which kernels the step runs: decided here, before anything is allocated (route.resolve_route holds the table of
+        # flags and switches); every flag is also an attribute of the engine (eng.tail2, eng.attn_fused, ...)
+        self.route: Route = resolve_route(compute_dtype, self.C, self.S, self.p, self.D, self.H, self.hid, self.Lyr, self.Cn,
+                                          extras=extras, fuse_ln=fuse_ln)
+        self.__dict__.update(dataclasses.asdict(self.route))
         self._save_hidden = True
-        # the 32x32-tile forward kernel (csrc/attn32.hip) for the benchmark geometry; VITPE_ATTN_WIDE=0: the 16x16-tile one
-        self.attn_wide = (self.attn_fused and K.fused_attention_wide_supported(self.T, self.N, self.D, self.D // self.H)
-                          and os.environ.get("VITPE_ATTN_WIDE", "1") == "1")
-        # ViT-B/16 geometry (hd = 64, N = 197): qkv projection + PE + core in one kernel (csrc/attn_core.hip,
-        # attn_fused64_fwd_kernel); the raw projection is still written once in training -- the core backward reads it.
-        # VITPE_ATTN_FUSED64=0: vitpe_linear + vitpe_attention_core_fwd
-        self.attn_fused64 = (not self.attn_fused and not self.extras and os.environ.get("VITPE_ATTN_FUSED64", "1") == "1"
-                             and K.attention_fused64_supported(self.T, self.N, self.H, self.D // self.H))
-        if not self.attn_fused:   # the LayerNorm / MLP fusions hang off the fused attention kernels' geometry
-            self.fuse_ln = self.fuse_ln_bwd = False
-        # block tail (attn.proj + residual + LayerNorm2 + MLP branch) as one kernel per direction: a wave per 16-token
-        # tile, hidden activation in registers, weights as fragment-packed shadows, gelu'(u) saved (IEEE half) instead
-        # of u.  VITPE_TAIL2=0: the per-Linear panel GEMMs (the comparator tests/test_bench_path_gpu.py runs against)
-        self.tail2 = (self.fuse_ln and self.fuse_ln_bwd and os.environ.get("VITPE_TAIL2", "1") == "1"
-                      and K.block_tail2_supported(self.T, self.D, self.hid))
-        # qkv data gradient + LayerNorm1 backward on the same mapping (29.5 vs 31.4 us for the panel kernel; VITPE_LNBWD2=0:
-        # the panel kernel on the transposed shadow)
-        self.lnbwd2 = self.tail2 and os.environ.get("VITPE_LNBWD2", "1") == "1"
-        # ... and run as the PROLOGUE of the block below's tail backward (one kernel per layer boundary; VITPE_FUSE_LNBWD=0: two)
-        self.fuse_lnbwd = self.lnbwd2 and os.environ.get("VITPE_FUSE_LNBWD", "1") == "1"
+        self._ticked = False                               # _loss(tick=True) on the fused head advanced the step counter
+        self._eval_ctl = self._eval_ctl_key = None         # eval_loss's scalars, per distinct batch shape
+        self.clip_max_norm = self._clip_partial = None     # set_grad_clip(): None = clipping off; the clip's work buffer
         self._build_flat(lr, weight_decay, betas, eps)
         self._build_buffers()
         self._build_rng_table()
@@ -168,8 +138,15 @@ class TrainEngine:
         # host.  Off by default: RCCL capture has not run on hardware yet (no multi-GPU lease this round either) -- the
         # stitched path only uses plain torch.distributed calls.  A failed capture falls back to it.
         self.ddp_graph = self.world > 1 and os.environ.get("VITPE_DDP_GRAPH", "0") == "1"
-        self.graph_fb = self.graph_fb2 = self.graph_opt = None
+        self._drop_graphs()
         self.steps_done = 0
+
+    def _drop_graphs(self):
+        """Forget the captured step: the next step() captures again."""
+        self.graph_fb = self.graph_fb2 = self.graph_opt = None
+
+    def _rank(self) -> int:
+        return dist.get_rank(self.pg) if self.world > 1 else 0
 
     # ---------------------------------------------------------------- parameters / shadows
     def _build_flat(self, lr, wd, betas, eps):
@@ -192,76 +169,30 @@ class TrainEngine:
         self.hp = torch.zeros(16, **f)
         self.hp[:5] = torch.tensor([lr, betas[0], betas[1], eps, wd], **f)
         self.hp[8] = 1.0 / self.world
-        # transposed shadows of the GEMM weights (data-gradient GEMMs) and fragment-major packed qkv
-        # weights (attention kernels): one flat buffer, refreshed by ONE batched kernel per step
-        self._st: Dict[int, torch.Tensor] = {}
-        self._pk: Dict[int, torch.Tensor] = {}
-        self._pkw: Dict[int, torch.Tensor] = {}
-        self._fr: Dict[int, torch.Tensor] = {}
-        self._frt: Dict[int, torch.Tensor] = {}
-        self._gemm_weights: List[nn.Parameter] = []
-        # one record per weight matrix, up to two shadows each (the source tile is loaded once for both)
-        recs, off, tile0 = [], 0, 0
-        def alloc(w):
-            nonlocal off
-            o = off
-            off += (w.numel() + ALIGN - 1) // ALIGN * ALIGN
-            return o
-        def add(w, kind, hd, kind2=-1, hd2=0):
-            nonlocal tile0
-            R, C = w.shape
-            o1 = alloc(w)
-            o2 = alloc(w) if kind2 >= 0 else 0
-            recs.append((self._off[id(w)], o1, o2, R, C, tile0, kind, hd, kind2, hd2, 0))
-            tile0 += ((R + 31) // 32) * ((C + 31) // 32)
-            spans.append((w, kind, o1))
-            if kind2 >= 0:
-                spans.append((w, kind2, o2))
-        spans = []
-        HDh = self.D // self.H
-        gen2 = self.tail2
-        for blk in self.model.blocks:
-            qkv, proj, fc1, fc2 = blk.attn.qkv.weight, blk.attn.proj.weight, blk.mlp.fc1.weight, blk.mlp.fc2.weight
-            self._gemm_weights += [qkv, proj, fc1, fc2]
-            # kind 0 transposed shadow (first-generation data-gradient GEMMs), 1 qkv pack (attention), 2 / 3 fragment packs
-            # (block_tail2_fwd), 4 / 5 fragment packs of the transposes (block_tail2_bwd, linear_lnbwd2)
-            if self.attn_fused:
-                add(qkv, 1, HDh, *((4, 64) if self.lnbwd2 else (0, 0)))
-                if self.attn_wide:
-                    add(qkv, 6, HDh)
+        # transposed shadows of the GEMM weights (data-gradient GEMMs) and fragment-major packed copies (attention and
+        # block-tail kernels): one flat buffer laid out by route.shadow_plan, refreshed by ONE batched kernel per step
+        blocks = [(b.attn.qkv.weight, b.attn.proj.weight, b.mlp.fc1.weight, b.mlp.fc2.weight) for b in self.model.blocks]
+        self._gemm_weights: List[nn.Parameter] = [w for ws in blocks for w in ws]
+        rec, spans, tmap, total = shadow_plan(self.route, [[tuple(w.shape) for w in ws] for ws in blocks],
+                                              [[offs[id(w)] for w in ws] for ws in blocks], self.D // self.H)
+        self._shadow_flat = torch.empty(total, dtype=self.T, device=self.dev)
+        # views by id(weight): KIND_T; KIND_QKV; KIND_QKV_WIDE; KIND_FRAG, KIND_FRAG_PHI; KIND_FRAG_T, KIND_FRAG_T_PHI
+        self._st, self._pk, self._pkw, self._fr, self._frt = ({} for _ in range(5))   # type: Dict[int, torch.Tensor]
+        for wi, kind, o in spans:
+            w = self._gemm_weights[wi]
+            (R, C), flat = w.shape, self._shadow_flat[o:o + w.numel()]
+            if kind == KIND_T:
+                self._st[id(w)] = flat.view(C, R)
+            elif kind == KIND_QKV:
+                self._pk[id(w)] = flat.view(R, C)
+            elif kind == KIND_QKV_WIDE:
+                self._pkw[id(w)] = flat
+            elif kind in (KIND_FRAG, KIND_FRAG_PHI):
+                self._fr[id(w)] = flat.view(R, C)
             else:
-                add(qkv, 0, 0, *((2, 64) if self.attn_fused64 else ()))
-            if self.tail2:
-                add(proj, 2, 192, *((5, 192) if gen2 else (0, 0)))
-                add(fc1, 3, 192, *((5, 32) if gen2 else (0, 0)))
-                add(fc2, 3, 32, *((5, 192) if gen2 else (0, 0)))
-            else:
-                for w in (proj, fc1, fc2):
-                    add(w, 0, 0)
-        self._shadow_flat = torch.empty(off, dtype=self.T, device=self.dev)
-        for w, kind, o in spans:
-            R, C = w.shape
-            if kind == 0:
-                self._st[id(w)] = self._shadow_flat[o:o + R * C].view(C, R)
-            elif kind == 1:
-                self._pk[id(w)] = self._shadow_flat[o:o + R * C].view(R, C)
-            elif kind == 6:
-                self._pkw[id(w)] = self._shadow_flat[o:o + R * C]
-            elif kind < 4:
-                self._fr[id(w)] = self._shadow_flat[o:o + R * C].view(R, C)
-            else:
-                self._frt[id(w)] = self._shadow_flat[o:o + R * C].view(C, R)
-        import numpy as np
-        rec = np.zeros(len(recs), dtype=np.dtype([("src", "<i8"), ("dst", "<i8"), ("dst2", "<i8"), ("R", "<i4"), ("C", "<i4"),
-                                                   ("tile0", "<i4"), ("kind", "<i4"), ("HD", "<i4"), ("kind2", "<i4"),
-                                                   ("HD2", "<i4"), ("pad", "<i4")]))
-        for i, r in enumerate(recs):
-            rec[i] = r
+                self._frt[id(w)] = flat.view(C, R)
         self._desc = torch.from_numpy(rec.view(np.uint8).copy()).to(self.dev)
-        self._ndesc, self._ntiles = len(recs), tile0
-        tmap = np.zeros(tile0, dtype=np.int16)
-        for i, r in enumerate(recs):
-            tmap[r[5]:] = i
+        self._ndesc, self._ntiles = len(rec), len(tmap)
         self._tile_map = torch.from_numpy(tmap).to(self.dev)
         self.refresh_shadows()
 
@@ -287,16 +218,23 @@ class TrainEngine:
     def Pkw(self, prm):  # wide pack of the qkv weights (32x32-tile attention forward)
         return self._pkw[id(prm)]
 
+    def Fr(self, prm):  # fragment-major packed copy (block_tail2_fwd)
+        return self._fr[id(prm)]
+
+    def Frt(self, prm):  # fragment-major packed copy of the transpose (block_tail2_bwd)
+        return self._frt[id(prm)]
+
     def _attn_fwd(self, x, blk, out, ln=None, xn_out=None):
         """The fused attention forward the step runs: the wide kernel where its geometry applies."""
         if self.attn_wide:
             return K.fused_attention_fwd_wide(x, self.Pkw(blk.attn.qkv.weight), self.H, self.pe, out=out, ln=ln, xn_out=xn_out)
         return K.fused_attention_fwd(x, self.Pk(blk.attn.qkv.weight), self.H, self.pe, out=out, ln=ln, xn_out=xn_out)
 
-    def _attn_layer_fwd(self, l, save_qkv=True):
+    def _attn_layer_fwd(self, l, save_qkv=True, p_drop=0.):
         """Layer l's attention forward as the step runs it, on the layer's own buffers: fused (LayerNorm staged inside when
         fuse_ln), projection + core in one kernel at hd = 64 (save_qkv: the raw projection goes to qkv_l[l] for the
-        backward), or the core on qkv_l[l] -- the qkv Linear in front of that one is the caller's."""
+        backward), or the core on qkv_l[l] -- the qkv Linear in front of that one is the caller's -- with attention
+        dropout at rate p_drop inside it (extras)."""
         blk, a = self.model.blocks[l], self.act[l]
         if self.fuse_ln:   # (xn1 is None when recompute_ln)
             return self._attn_fwd(self.x[l], blk, a["a"], ln=(blk.norm1.weight.data, blk.norm1.bias.data, a["m1"], a["r1"]),
@@ -306,12 +244,18 @@ class TrainEngine:
         if self.attn_fused64:
             return K.attention_fused64_fwd(a["xn1"], self.Fr(blk.attn.qkv.weight), self.H, self.pe,
                                            qkv_out=(self.qkv_l[l] if save_qkv else None), out=a["a"])
+        if p_drop > 0.:
+            return K.attention_core_fwd_drop(self.qkv_l[l], self.H, self.pe, self._site(l, SITE_ATTN, p_drop), p_drop,
+                                             out=a["a"])
         return K.attention_core_fwd(self.qkv_l[l], self.H, self.pe, out=a["a"])
 
-    def _attn_bwd(self, l, dout):
+    def _attn_bwd(self, l, dout, p_drop=0.):
         """Layer l's attention backward as the step runs it: dout (gradient of the merged heads) -> dqkv_l[l], PE-parameter
-        gradients accumulated."""
+        gradients accumulated; p_drop: the forward's attention dropout, its mask regenerated."""
         blk, a = self.model.blocks[l], self.act[l]
+        if not self.attn_fused and p_drop > 0.:
+            return K.attention_core_bwd_drop(self.qkv_l[l], dout, self.H, self.pe, self._site(l, SITE_ATTN, p_drop), p_drop,
+                                             out=self.dqkv_l[l], **self.pe_grads)
         if not self.attn_fused:
             return K.attention_core_bwd(self.qkv_l[l], dout, self.H, self.pe, out=self.dqkv_l[l], **self.pe_grads)
         if self.recompute_ln:   # nothing normalised was stored: LayerNorm1 again while staging the raw tokens
@@ -320,12 +264,6 @@ class TrainEngine:
         return K.fused_attention_bwd(a["xn1"], self.Pk(blk.attn.qkv.weight), dout, self.H, self.pe, out=self.dqkv_l[l],
                                      **self.pe_grads)
 
-    def Fr(self, prm):  # fragment-major packed copy (block_tail2_fwd)
-        return self._fr[id(prm)]
-
-    def Frt(self, prm):  # fragment-major packed copy of the transpose (block_tail2_bwd)
-        return self._frt[id(prm)]
-
     def refresh_shadows(self, cast_flat=True):
         if self.T == torch.bfloat16 and cast_flat:
             K.cast(self.flat_p, torch.bfloat16, out=self.flat_s)
@@ -333,9 +271,6 @@ class TrainEngine:
 
     def set_lr(self, lr: float):
         self.hp[0] = lr
-
-    clip_max_norm: Optional[float] = None   # set_grad_clip(); None = clipping off
-    _clip_partial = None                    # grad_clip's work buffer, allocated on the first enable
 
     def set_grad_clip(self, max_norm: Optional[float]):
         """torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) between the backward (after every all-reduce) and
@@ -353,7 +288,7 @@ class TrainEngine:
                 self._clip_partial = torch.zeros(K.grad_clip_blocks(self.n_flat), dtype=torch.float32, device=self.dev)
             self.hp[12] = new
         if (new is None) != (self.clip_max_norm is None):
-            self.graph_fb = self.graph_fb2 = self.graph_opt = None
+            self._drop_graphs()
         self.clip_max_norm = new
 
     def grad_norm(self) -> float:
@@ -374,14 +309,6 @@ class TrainEngine:
         self.labels = torch.zeros(B, dtype=torch.int64, device=dev)
         self.patches = e(B * self.P, self.C * self.p * self.p)
         self.x = [e(B, N, D) for _ in range(self.Lyr + 1)]
-        # weight gradients: one grouped launch per backward part (default) or one GEMM per nn.Linear
-        self.group_wgrad = os.environ.get("VITPE_GROUP_WGRAD", "1") == "1"
-        # VITPE_RECOMPUTE_LN=1: LayerNorm outputs are not stored at all -- the attention backward and the weight-gradient
-        # kernel re-normalise the raw rows from the saved statistics while staging them (-25.6 MB of stores per layer).
-        # Measured neutral-to-slower (the statistics loads cost the weight-gradient kernel, which lives on the vector-
-        # memory path, +55..75 us per step; the forward kernels gain ~20 us): off by default, kept for memory-bound boxes.
-        self.recompute_ln = (self.attn_fused and self.fuse_ln and self.fuse_ln_bwd and self.tail2
-                             and self.group_wgrad and os.environ.get("VITPE_RECOMPUTE_LN", "0") == "1")
         xn = (lambda: None) if self.recompute_ln else (lambda: e(B, N, D))
         self.act = []
         for blk in self.model.blocks:
@@ -398,19 +325,7 @@ class TrainEngine:
         self._valid = None
         self.set_valid(B)
         self.head_scratch = torch.zeros(2 * B, dtype=torch.float32, device=dev)   # (loss, correct) per image
-        # one-launch head + CE + head backward (vitpe_head_step; r1's vitpe_head_loss was 45 us against 40 us for the
-        # three small kernels: its class loop serialised ten wave reductions per image).  VITPE_FUSE_HEAD=0: three kernels.
-        self.fuse_head = self.Cn <= 64 and self.D <= 768 and os.environ.get("VITPE_FUSE_HEAD", "1") == "1"
         self.head_ws = (f(B, D), f(B, D), f(B))
-        # Class-row mode of the TOP block ("Top block on the class-token rows").  The model pools the class token (vit.py: the head reads x[:, 0]): of
-        # x[L] only row b * N is read, of dx_out[L] only that row is non-zero, so the top block's tail, its backward and its
-        # fc2 / fc1 / proj weight gradients run on the B class rows (csrc/tail_cls.hip, row-step problems in csrc/wgrad.hip).
-        # The invariant that replaces the zeros the full-row backward used to write: the non-class rows of du_l[L-1],
-        # dx_mid[L-1] and da_top are zeroed HERE and never written again (the attention backward, the block below's prologue
-        # and the qkv weight gradient sum over all rows).  VITPE_CLS_ROWS=0: the full-row kernels.
-        # (not for a one-layer model: its top block's du_l[0] is self.du, which bench.py's probes write in full)
-        self.cls_rows = (self.tail2 and self.group_wgrad and self.fuse_head and T == torch.bfloat16 and self.Lyr >= 2
-                         and os.environ.get("VITPE_CLS_ROWS", "1") == "1")
         self._probe_scratch = None
         self.ws_dyn = f(B, D)
         # Gradient tensors read by the weight-gradient GEMMs get per-layer buffers (dy = d x_out, dmid = d x_mid,
@@ -429,6 +344,12 @@ class TrainEngine:
         self.g1_l = [e(B, N, D) if on(blk, blk.attn.proj_drop_p) else None for blk in self.model.blocks]
         self.dqkv, self.du = self.dqkv_l[0], self.du_l[0]          # (bench.py times the kernels on these)
         self.da_top = None
+        # Class-row mode of the TOP block (route.cls_rows; DESIGN.md 4, "Top block on the class-token rows").  The model
+        # pools the class token: of x[L] only row b * N is read, of dx_out[L] only that row is non-zero, so the top block's
+        # tail, its backward and its fc2 / fc1 / proj weight gradients run on the B class rows.  The invariant that replaces
+        # the zeros the full-row backward used to write: the non-class rows of du_l[L-1], dx_mid[L-1] and da_top are zeroed
+        # HERE and never written again (the attention backward, the block below's prologue and the qkv weight gradient sum
+        # over all rows).  (Not for a one-layer model: its du_l[0] is self.du, which bench.py's probes write in full.)
         if self.cls_rows:
             # the top block's own d(attention output): dtmp is shared with the layers below, which overwrite every row
             self.da_top = torch.zeros(B, N, D, dtype=T, device=dev)
@@ -469,8 +390,7 @@ class TrainEngine:
         self.rng_table = None
         if not self.extras:
             return
-        rank = dist.get_rank(self.pg) if self.world > 1 else 0
-        self.rng_table = shift_rng_offsets(K.new_rng_pairs(SITES_PER_LAYER * self.Lyr, self.dev), rank)
+        self.rng_table = shift_rng_offsets(K.new_rng_pairs(SITES_PER_LAYER * self.Lyr, self.dev), self._rank())
         self._rng_rows = [self.rng_table[i] for i in range(self.rng_table.shape[0])]   # views: set_rng_table copies in place
 
     def set_rng_table(self, table: torch.Tensor):
@@ -500,9 +420,9 @@ class TrainEngine:
         elif rng is not None:
             self.aug_rng = rng.to(self.dev).reshape(1, 2).clone()
         else:
-            self.aug_rng = new_augment_rng(self.dev, dist.get_rank(self.pg) if self.world > 1 else 0)
+            self.aug_rng = new_augment_rng(self.dev, self._rank())
         self.aug_pad, self.aug_hflip = crop_pad, hflip
-        self.graph_fb = self.graph_fb2 = self.graph_opt = None
+        self._drop_graphs()
 
     def _site(self, l, site, rate):
         """The site's row of the table, or None where its rate is 0 (nothing is launched for it)."""
@@ -518,18 +438,40 @@ class TrainEngine:
         K.linear(inp, self.Sh(lin.weight), lin.bias.data, out=self.dtmp.view(M, D))
         K.branch_drop_fwd(self.dtmp, self._site(l, site_e, p_e), p_e, self._site(l, site_p, p_p), p_p, resid=resid, out=out)
 
-    def _extras_layer_fwd(self, l, train):
-        """Layer l on the per-Linear route; train: the dropout sites run at the model's rates (evaluation: none does)."""
+    # ---------------------------------------------------------------- one layer, forward
+    def _layer_fwd(self, l, train):
+        """Layer l in one of three shapes: LayerNorm-fused attention + the block tail (tail2); LayerNorm-fused attention +
+        the panel kernels (fuse_ln); the plain per-Linear chain (extras, and every geometry without the fusions)."""
+        if not self.fuse_ln:
+            return self._plain_layer_fwd(l, train)
+        mdl, blk, a, M, D = self.model, self.model.blocks[l], self.act[l], self.M, self.D
+        # LN1 inside the attention kernel's token staging; LN2 inside fc1's operand staging; their statistics come out of
+        # the producing GEMM's epilogue (proj / previous fc2)
+        self._attn_layer_fwd(l)
+        nxt = (self.act[l + 1]["m1"], self.act[l + 1]["r1"]) if l + 1 < self.Lyr else None
+        if self.tail2:   # proj + residual + LN2 + MLP branch: one kernel per block tail
+            return self._block_tail_fwd(l, blk, a, nxt)
+        K.linear(a["a"].view(M, D), self.Sh(blk.attn.proj.weight), blk.attn.proj.bias.data, epi=L.EPI_BIAS_RESID,
+                 resid=self.x[l].view(M, D), out=a["xmid"].view(M, D), stats=(a["m2"], a["r2"]), eps=blk.norm2.eps)
+        K.linear_ln(a["xmid"].view(M, D), blk.norm2.weight.data, blk.norm2.bias.data, a["m2"], a["r2"],
+                    self.Sh(blk.mlp.fc1.weight), blk.mlp.fc1.bias.data, epi=L.EPI_BIAS_GELU, u=a["u"], out=a["h"],
+                    xn_out=a["xn2"].view(M, D))
+        K.linear(a["h"], self.Sh(blk.mlp.fc2.weight), blk.mlp.fc2.bias.data, epi=L.EPI_BIAS_RESID,
+                 resid=a["xmid"].view(M, D), out=self.x[l + 1].view(M, D), stats=nxt,
+                 eps=mdl.blocks[min(l + 1, self.Lyr - 1)].norm1.eps)
+
+    def _plain_layer_fwd(self, l, train):
+        """LayerNorm, qkv Linear, attention, proj + residual, LayerNorm, fc1 + GELU, fc2 + residual, one launch each.
+        train: the dropout sites run at the model's rates (evaluation: none does); a site whose rate is 0 and an absent
+        qkv bias launch nothing, so a model without them runs the bare chain."""
         blk, a, xin, M, D = self.model.blocks[l], self.act[l], self.x[l], self.M, self.D
         p_attn, p_proj, p_mlp, p_path = self.rates[l] if train else (0., 0., 0., 0.)
         K.layernorm_fwd(xin, blk.norm1.weight.data, blk.norm1.bias.data, blk.norm1.eps, out=a["xn1"], mean=a["m1"], rstd=a["r1"])
-        bq = blk.attn.qkv.bias
-        K.linear(a["xn1"].view(M, D), self.Sh(blk.attn.qkv.weight), None if bq is None else bq.data,
-                 out=self.qkv_l[l].view(M, 3 * D))
-        if p_attn > 0.:
-            K.attention_core_fwd_drop(self.qkv_l[l], self.H, self.pe, self._site(l, SITE_ATTN, p_attn), p_attn, out=a["a"])
-        else:
-            K.attention_core_fwd(self.qkv_l[l], self.H, self.pe, out=a["a"])
+        if not self.attn_fused and not self.attn_fused64:
+            bq = blk.attn.qkv.bias
+            K.linear(a["xn1"].view(M, D), self.Sh(blk.attn.qkv.weight), None if bq is None else bq.data,
+                     out=self.qkv_l[l].view(M, 3 * D))
+        self._attn_layer_fwd(l, save_qkv=self._save_hidden, p_drop=p_attn)
         self._branch_fwd(l, a["a"].view(M, D), blk.attn.proj, xin, a["xmid"], SITE_PROJ, p_proj, SITE_PATH_A, p_path)
         K.layernorm_fwd(a["xmid"], blk.norm2.weight.data, blk.norm2.bias.data, blk.norm2.eps, out=a["xn2"], mean=a["m2"],
                         rstd=a["r2"])
@@ -540,45 +482,73 @@ class TrainEngine:
             h = K.dropout_fwd(a["h"], self._site(l, SITE_MLP1, p_mlp), p_mlp, out=a["hd"])
         self._branch_fwd(l, h, blk.mlp.fc2, a["xmid"], self.x[l + 1], SITE_MLP2, p_mlp, SITE_PATH_M, p_path)
 
-    def _extras_layer_bwd(self, l):
-        """Backward of _extras_layer_fwd(l, train=True): every mask regenerated from the table's rows."""
+    # ---------------------------------------------------------------- one layer, backward: four steps
+    def _layer_bwd(self, l, lo, hi):
+        """Backward of layer l within a part that spans layers lo..hi.  With fuse_lnbwd the last step of layer l runs as the
+        prologue of layer l - 1's first (one kernel per layer boundary inside the part); per-GEMM weight gradients would
+        read dx_out[l] before that kernel has written it, so the pairing needs the grouped launch."""
+        paired = self.fuse_lnbwd and self.group_wgrad
+        self._mlp_bwd(l, pre=paired and l < hi)
+        self._proj_bwd(l)
+        self._attn_bwd(l, self.da_top if self._top_cls(l) else self.dtmp, p_drop=self.rates[l][0])
+        self._gemm_tn(l, "qkv")
+        if not (paired and l > lo):
+            self._qkv_bwd(l)
+
+    def _mlp_bwd(self, l, pre=False):
+        """x_out = xmid + drop_path(drop2(fc2(drop1(gelu(fc1(LN2(xmid))))))): dx_out[l + 1] -> du_l[l], dx_mid[l].  tail2: one
+        kernel, which also leaves the projection's data gradient in dtmp (da_top in class-row mode)."""
         blk, a, M, D, G = self.model.blocks[l], self.act[l], self.M, self.D, self.Gr
-        p_attn, p_proj, p_mlp, p_path = self.rates[l]
-        dy3, dmid3, du, dqkv = self.dx_out[l + 1], self.dx_mid[l], self.du_l[l], self.dqkv_l[l]
-        # ---- MLP branch: x_out = xmid + drop_path(drop2(fc2(drop1(gelu(fc1(LN2(xmid)))))))
+        _, _, p_mlp, p_path = self.rates[l]
+        dy3, dmid3, du = self.dx_out[l + 1], self.dx_mid[l], self.du_l[l]
         g2 = dy3
         if self.g2_l[l] is not None:   # fc2's dY: per layer, the grouped weight-gradient launch reads it after the chain
             g2 = K.branch_drop_bwd(dy3, self._site(l, SITE_MLP2, p_mlp), p_mlp, self._site(l, SITE_PATH_M, p_path), p_path,
                                    out=self.g2_l[l])
-        g2 = g2.view(M, D)
-        hx = a["hd"] if a["hd"] is not None else a["h"]
-        self._wgrad(lambda: K.gemm_tn(g2, hx, G(blk.mlp.fc2.weight), G(blk.mlp.fc2.bias)))
-        K.linear(g2, self.St(blk.mlp.fc2.weight), None, epi=L.EPI_GELU_BWD, u=a["u"], out=du)
+        self._gemm_tn(l, "fc2")
+        if self.tail2:   # gelu' + both data gradients + LayerNorm2 backward + residual + the projection's data gradient
+            self._block_tail_bwd(l, blk, a, pre=pre)
+            self._gemm_tn(l, "fc1")
+            return
+        K.linear(g2.view(M, D), self.St(blk.mlp.fc2.weight), None, epi=L.EPI_GELU_BWD, u=a["u"], out=du)
         if p_mlp > 0.:   # (g2 W2) . gelu'(u) . m1 / (1 - p): the two elementwise factors commute
             K.dropout_bwd(du, self._site(l, SITE_MLP1, p_mlp), p_mlp, out=du)
-        self._wgrad(lambda: K.gemm_tn(du, a["xn2"].view(M, D), G(blk.mlp.fc1.weight), G(blk.mlp.fc1.bias)))
+        self._gemm_tn(l, "fc1")
+        if self.fuse_ln_bwd:   # data gradient of fc1 + LayerNorm2 backward + residual add in one kernel
+            K.linear_lnbwd(du, self.St(blk.mlp.fc1.weight), a["xmid"].view(M, D), a["m2"], a["r2"], blk.norm2.weight.data,
+                           dy3.view(M, D), G(blk.norm2.weight), G(blk.norm2.bias), out=dmid3.view(M, D))
+            return
         K.linear(du, self.St(blk.mlp.fc1.weight), None, out=self.dtmp.view(M, D))
         K.layernorm_bwd(self.dtmp, a["xmid"], a["m2"], a["r2"], blk.norm2.weight.data, G(blk.norm2.weight), G(blk.norm2.bias),
                         dres=dy3, out=dmid3, workspace=self.ln_ws)
-        # ---- attention branch: xmid = x_in + drop_path(proj_drop(proj(attn(LN1(x_in)))))
-        g1 = dmid3
+
+    def _proj_bwd(self, l):
+        """xmid = x_in + drop_path(proj_drop(proj(attn))): dx_mid[l] -> dtmp, the gradient of the merged heads (tail2: the
+        tail backward has already written it)."""
+        blk, M, D = self.model.blocks[l], self.M, self.D
+        _, p_proj, _, p_path = self.rates[l]
+        g1 = self.dx_mid[l]
         if self.g1_l[l] is not None:
-            g1 = K.branch_drop_bwd(dmid3, self._site(l, SITE_PROJ, p_proj), p_proj, self._site(l, SITE_PATH_A, p_path), p_path,
+            g1 = K.branch_drop_bwd(g1, self._site(l, SITE_PROJ, p_proj), p_proj, self._site(l, SITE_PATH_A, p_path), p_path,
                                    out=self.g1_l[l])
-        g1 = g1.view(M, D)
-        self._wgrad(lambda: K.gemm_tn(g1, a["a"].view(M, D), G(blk.attn.proj.weight), G(blk.attn.proj.bias)))
-        K.linear(g1, self.St(blk.attn.proj.weight), None, out=self.dtmp.view(M, D))
-        if p_attn > 0.:
-            K.attention_core_bwd_drop(self.qkv_l[l], self.dtmp, self.H, self.pe, self._site(l, SITE_ATTN, p_attn), p_attn,
-                                      out=dqkv, **self.pe_grads)
+        self._gemm_tn(l, "proj")
+        if not self.tail2:
+            K.linear(g1.view(M, D), self.St(blk.attn.proj.weight), None, out=self.dtmp.view(M, D))
+
+    def _qkv_bwd(self, l):
+        """dqkv_l[l] -> dx_out[l]: the qkv data gradient, LayerNorm1 backward and the residual add."""
+        blk, a, M, D, G = self.model.blocks[l], self.act[l], self.M, self.D, self.Gr
+        dqkv, dm = self.dqkv_l[l].view(M, 3 * D), self.dx_mid[l].view(M, D)
+        if self.lnbwd2:          # one kernel on the wave-per-tile mapping, packed qkv.weight^T
+            K.linear_lnbwd2(dqkv, self.Frt(blk.attn.qkv.weight), self.x[l].view(M, D), a["m1"], a["r1"], blk.norm1.weight.data,
+                            dm, G(blk.norm1.weight), G(blk.norm1.bias), out=self.dx_out[l].view(M, D))
+        elif self.fuse_ln_bwd:   # one panel kernel on the transposed shadow
+            K.linear_lnbwd(dqkv, self.St(blk.attn.qkv.weight), self.x[l].view(M, D), a["m1"], a["r1"], blk.norm1.weight.data,
+                           dm, G(blk.norm1.weight), G(blk.norm1.bias), out=self.dx_out[l].view(M, D))
         else:
-            K.attention_core_bwd(self.qkv_l[l], self.dtmp, self.H, self.pe, out=dqkv, **self.pe_grads)
-        bq = blk.attn.qkv.bias
-        self._wgrad(lambda: K.gemm_tn(dqkv.view(M, 3 * D), a["xn1"].view(M, D), G(blk.attn.qkv.weight),
-                                      None if bq is None else G(bq)))
-        K.linear(dqkv.view(M, 3 * D), self.St(blk.attn.qkv.weight), None, out=self.dtmp.view(M, D))
-        K.layernorm_bwd(self.dtmp, self.x[l], a["m1"], a["r1"], blk.norm1.weight.data, G(blk.norm1.weight), G(blk.norm1.bias),
-                        dres=dmid3, out=self.dx_out[l], workspace=self.ln_ws)
+            K.linear(dqkv, self.St(blk.attn.qkv.weight), None, out=self.dtmp.view(M, D))
+            K.layernorm_bwd(self.dtmp, self.x[l], a["m1"], a["r1"], blk.norm1.weight.data, G(blk.norm1.weight),
+                            G(blk.norm1.bias), dres=self.dx_mid[l], out=self.dx_out[l], workspace=self.ln_ws)
 
     # ---------------------------------------------------------------- forward / backward
     def _forward(self, head=True, save=False, train=False):
@@ -614,42 +584,8 @@ class TrainEngine:
                                 rstd=self.act[0]["r1"], stats_only=True)
         if isinstance(mdl.pos_embed, RoPEMixed):  # learnable frequencies: tables follow the parameters
             K.rope_mixed_tables(mdl.pos_embed.freqs.data, self.grid, self.pe.cos, self.pe.sin)
-        for l, blk in enumerate(mdl.blocks):
-            a, xin = self.act[l], self.x[l]
-            if self.extras:
-                self._extras_layer_fwd(l, train)
-                continue
-            if self.fuse_ln:
-                # LN1 inside the attention kernel's token staging; LN2 inside fc1's operand staging; their
-                # statistics come out of the producing GEMM's epilogue (proj / previous fc2)
-                self._attn_layer_fwd(l)
-                nxt = (self.act[l + 1]["m1"], self.act[l + 1]["r1"]) if l + 1 < self.Lyr else None
-                eps_next = mdl.blocks[min(l + 1, self.Lyr - 1)].norm1.eps
-                if self.tail2:   # proj + residual + LN2 + MLP branch: one kernel per block tail
-                    self._block_tail_fwd(l, blk, a, nxt)
-                    continue
-                K.linear(a["a"].view(M, D), self.Sh(blk.attn.proj.weight), blk.attn.proj.bias.data,
-                         epi=L.EPI_BIAS_RESID, resid=xin.view(M, D), out=a["xmid"].view(M, D), stats=(a["m2"], a["r2"]),
-                         eps=blk.norm2.eps)
-                K.linear_ln(a["xmid"].view(M, D), blk.norm2.weight.data, blk.norm2.bias.data, a["m2"], a["r2"],
-                            self.Sh(blk.mlp.fc1.weight), blk.mlp.fc1.bias.data, epi=L.EPI_BIAS_GELU, u=a["u"], out=a["h"],
-                            xn_out=a["xn2"].view(M, D))
-                K.linear(a["h"], self.Sh(blk.mlp.fc2.weight), blk.mlp.fc2.bias.data, epi=L.EPI_BIAS_RESID,
-                         resid=a["xmid"].view(M, D), out=self.x[l + 1].view(M, D), stats=nxt, eps=eps_next)
-                continue
-            K.layernorm_fwd(xin, blk.norm1.weight.data, blk.norm1.bias.data, blk.norm1.eps, out=a["xn1"],
-                            mean=a["m1"], rstd=a["r1"])
-            if not self.attn_fused and not self.attn_fused64:
-                K.linear(a["xn1"].view(M, D), self.Sh(blk.attn.qkv.weight), None, out=self.qkv_l[l].view(M, 3 * D))
-            self._attn_layer_fwd(l, save_qkv=self._save_hidden)
-            K.linear(a["a"].view(M, D), self.Sh(blk.attn.proj.weight), blk.attn.proj.bias.data, epi=L.EPI_BIAS_RESID,
-                     resid=xin.view(M, D), out=a["xmid"].view(M, D))
-            K.layernorm_fwd(a["xmid"], blk.norm2.weight.data, blk.norm2.bias.data, blk.norm2.eps, out=a["xn2"],
-                            mean=a["m2"], rstd=a["r2"])
-            K.linear(a["xn2"].view(M, D), self.Sh(blk.mlp.fc1.weight), blk.mlp.fc1.bias.data, epi=L.EPI_BIAS_GELU,
-                     u=a["u"], out=a["h"])
-            K.linear(a["h"], self.Sh(blk.mlp.fc2.weight), blk.mlp.fc2.bias.data, epi=L.EPI_BIAS_RESID,
-                     resid=a["xmid"].view(M, D), out=self.x[l + 1].view(M, D))
+        for l in range(self.Lyr):
+            self._layer_fwd(l, train)
         if head:
             K.head_fwd(self.x[-1], mdl.norm.weight.data, mdl.norm.bias.data, mdl.head.weight.data, mdl.head.bias.data,
                        mdl.norm.eps, save=True, logits=self.logits, ws=self.head_ws)
@@ -661,55 +597,39 @@ class TrainEngine:
         """save: keep gelu'(u) and gelu(u) for the backward (None: what the running _forward was asked for).
         scratch (kernel_probes, class-row mode): the FULL-row kernel of the top block, its outputs sent to these buffers."""
         M, D = self.M, self.D
-        eps_next = self.model.blocks[min(l + 1, self.Lyr - 1)].norm1.eps
         if save is None:
             save = self._save_hidden
-        if self._top_cls(l) and scratch is None:   # the class rows only, in place on the full-layout buffers
-            K.tail_cls_fwd(a["a"].view(M, D), self.x[l].view(M, D), self.Fr(blk.attn.proj.weight), blk.attn.proj.bias.data,
-                           blk.norm2.weight.data, blk.norm2.bias.data, self.Fr(blk.mlp.fc1.weight), blk.mlp.fc1.bias.data,
-                           self.Fr(blk.mlp.fc2.weight), blk.mlp.fc2.bias.data, self.B, self.N, a["xmid"].view(M, D), a["m2"],
-                           a["r2"], self.x[l + 1].view(M, D),
-                           xn_out=(a["xn2"].view(M, D) if (save and not self.recompute_ln) else None),
-                           gp=(a["u"].view(torch.float16) if save else None), h=(a["h"] if save else None), eps2=blk.norm2.eps)
-            return
         o = scratch if scratch is not None else dict(a, xout=self.x[l + 1])
-        K.block_tail2_fwd(a["a"].view(M, D), self.x[l].view(M, D), self.Fr(blk.attn.proj.weight),
-                          blk.attn.proj.bias.data, blk.norm2.weight.data, blk.norm2.bias.data,
-                          self.Fr(blk.mlp.fc1.weight), blk.mlp.fc1.bias.data, self.Fr(blk.mlp.fc2.weight),
-                          blk.mlp.fc2.bias.data, x_mid=o["xmid"].view(M, D), mean2=o["m2"], rstd2=o["r2"],
-                          xn_out=(o["xn2"].view(M, D) if (save and not self.recompute_ln) else None),
-                          gp=(o["u"].view(torch.float16) if save else None), h=(o["h"] if save else None), out=o["xout"].view(M, D),
-                          stats=nxt, eps2=blk.norm2.eps, eps_next=eps_next, save=save)
+        args = (a["a"].view(M, D), self.x[l].view(M, D), self.Fr(blk.attn.proj.weight), blk.attn.proj.bias.data,
+                blk.norm2.weight.data, blk.norm2.bias.data, self.Fr(blk.mlp.fc1.weight), blk.mlp.fc1.bias.data,
+                self.Fr(blk.mlp.fc2.weight), blk.mlp.fc2.bias.data)
+        outs = dict(x_mid=o["xmid"].view(M, D), mean2=o["m2"], rstd2=o["r2"], out=o["xout"].view(M, D),
+                    xn_out=(o["xn2"].view(M, D) if (save and not self.recompute_ln) else None),
+                    gp=(o["u"].view(torch.float16) if save else None), h=(o["h"] if save else None), eps2=blk.norm2.eps)
+        if self._top_cls(l) and scratch is None:   # the class rows only, in place on the full-layout buffers
+            K.tail_cls_fwd(*args, self.B, self.N, **outs)
+        else:
+            K.block_tail2_fwd(*args, stats=nxt, eps_next=self.model.blocks[min(l + 1, self.Lyr - 1)].norm1.eps, save=save,
+                              **outs)
 
     def _block_tail_bwd(self, l, blk, a, pre=False, scratch=None):
         """pre: the qkv data gradient + LayerNorm1 backward of block l + 1 run first in the same kernel and produce
         dx_out[l + 1] (this block's dy).  scratch: as in _block_tail_fwd."""
         M, D, G = self.M, self.D, self.Gr
+        o = scratch if scratch is not None else dict(a, du=self.du_l[l], dxmid=self.dx_mid[l])
+        args = (self.dx_out[l + 1].view(M, D), o["u"].view(torch.float16), self.Frt(blk.mlp.fc2.weight),
+                self.Frt(blk.mlp.fc1.weight), o["xmid"].view(M, D), o["m2"], o["r2"], blk.norm2.weight.data,
+                G(blk.norm2.weight), G(blk.norm2.bias), self.Frt(blk.attn.proj.weight))
+        outs = dict(du=o["du"], out=o["dxmid"].view(M, D))
         if self._top_cls(l) and scratch is None:
-            K.tail_cls_bwd(self.dx_out[l + 1].view(M, D), a["u"].view(torch.float16), self.Frt(blk.mlp.fc2.weight),
-                           self.Frt(blk.mlp.fc1.weight), a["xmid"].view(M, D), a["m2"], a["r2"], blk.norm2.weight.data,
-                           G(blk.norm2.weight), G(blk.norm2.bias), self.Frt(blk.attn.proj.weight), self.B, self.N,
-                           du=self.du_l[l], out=self.dx_mid[l].view(M, D), da=self.da_top.view(M, D))
-            return
-        if scratch is not None:
-            K.block_tail2_bwd(self.dx_out[l + 1].view(M, D), scratch["u"].view(torch.float16), self.Frt(blk.mlp.fc2.weight),
-                              self.Frt(blk.mlp.fc1.weight), scratch["xmid"].view(M, D), scratch["m2"], scratch["r2"],
-                              blk.norm2.weight.data, G(blk.norm2.weight), G(blk.norm2.bias), self.Frt(blk.attn.proj.weight),
-                              du=scratch["du"], out=scratch["dxmid"].view(M, D), da=self.dtmp.view(M, D))
-            return
-        if pre:
+            K.tail_cls_bwd(*args, self.B, self.N, da=self.da_top.view(M, D), **outs)
+        elif pre and scratch is None:
             up, ua = self.model.blocks[l + 1], self.act[l + 1]
             K.block_tail2_bwd_pre(self.dqkv_l[l + 1].view(M, 3 * D), self.Frt(up.attn.qkv.weight), self.x[l + 1].view(M, D),
                                   ua["m1"], ua["r1"], up.norm1.weight.data, self.dx_mid[l + 1].view(M, D), G(up.norm1.weight),
-                                  G(up.norm1.bias), self.dx_out[l + 1].view(M, D), a["u"].view(torch.float16), self.Frt(blk.mlp.fc2.weight),
-                                  self.Frt(blk.mlp.fc1.weight), a["xmid"].view(M, D), a["m2"], a["r2"], blk.norm2.weight.data,
-                                  G(blk.norm2.weight), G(blk.norm2.bias), self.Frt(blk.attn.proj.weight), du=self.du_l[l],
-                                  out=self.dx_mid[l].view(M, D), da=self.dtmp.view(M, D))
-            return
-        K.block_tail2_bwd(self.dx_out[l + 1].view(M, D), a["u"].view(torch.float16), self.Frt(blk.mlp.fc2.weight),
-                          self.Frt(blk.mlp.fc1.weight), a["xmid"].view(M, D), a["m2"], a["r2"], blk.norm2.weight.data,
-                          G(blk.norm2.weight), G(blk.norm2.bias), self.Frt(blk.attn.proj.weight), du=self.du_l[l],
-                          out=self.dx_mid[l].view(M, D), da=self.dtmp.view(M, D))
+                                  G(up.norm1.bias), *args, da=self.dtmp.view(M, D), **outs)
+        else:
+            K.block_tail2_bwd(*args, da=self.dtmp.view(M, D), **outs)
 
     def _tail_bytes(self, fwd: bool) -> int:
         """Algorithmic HBM bytes of one block-tail launch (what the kernel must read and write once)."""
@@ -738,44 +658,46 @@ class TrainEngine:
         K.cross_entropy_ctl(self.logits, self.labels, self.ce_ctl, dlogits=self.dlogits, out2=self.out2,
                             metric_acc=self.metric_acc)
 
-    def _wgrad_problems(self, lo, hi, with_embed):
-        """(dY, X, dW, dbias) of every nn.Linear weight gradient of layers lo..hi (+ the patch embedding)."""
-        mdl, D, M, G = self.model, self.D, self.M, self.Gr
-        probs = []
-        for l in range(hi, lo - 1, -1):
-            blk, a = mdl.blocks[l], self.act[l]
-            if self.recompute_ln:   # X operands LayerNorm2(x_mid) / LayerNorm1(x_in): re-normalised inside the kernel
-                fc1 = (self.du_l[l], a["xmid"].view(M, D), G(blk.mlp.fc1.weight), G(blk.mlp.fc1.bias),
-                       (a["m2"], a["r2"], blk.norm2.weight.data, blk.norm2.bias.data))
-                qkv = (self.dqkv_l[l].view(M, 3 * D), self.x[l].view(M, D), G(blk.attn.qkv.weight), None,
-                       (a["m1"], a["r1"], blk.norm1.weight.data, blk.norm1.bias.data))
-            else:
-                fc1 = (self.du_l[l], a["xn2"].view(M, D), G(blk.mlp.fc1.weight), G(blk.mlp.fc1.bias))
-                bq = blk.attn.qkv.bias   # (extras route only)
-                qkv = (self.dqkv_l[l].view(M, 3 * D), a["xn1"].view(M, D), G(blk.attn.qkv.weight), None if bq is None else G(bq))
-            # extras route: dY behind the branch's dropout / drop-path backward, X the dropped hidden activation
-            g2 = self.g2_l[l] if self.g2_l[l] is not None else self.dx_out[l + 1]
-            g1 = self.g1_l[l] if self.g1_l[l] is not None else self.dx_mid[l]
-            fc2 = (g2.view(M, D), a["hd"] if a["hd"] is not None else a["h"], G(blk.mlp.fc2.weight), G(blk.mlp.fc2.bias))
-            proj = (g1.view(M, D), a["a"].view(M, D), G(blk.attn.proj.weight), G(blk.attn.proj.bias))
-            if self._top_cls(l):   # their dY is zero outside the class rows: contract over rows b * N only (row step N)
-                fc2, fc1, proj = ((p + (None,) * (5 - len(p)) + (self.N,)) for p in (fc2, fc1, proj))
-            probs += [fc2, fc1, proj, qkv]
-        if with_embed:
-            probs.append((self.dpatch, self.patches, G(mdl.patch_embed.weight).view(D, -1), G(mdl.patch_embed.bias)))
-        return probs
+    def _wgrad_problems(self, l):
+        """Layer l's four nn.Linear weight gradients as (dY, X, dW, dbias[, ln[, row_step]]), in launch order: the operands
+        of the grouped launch and of the per-Linear comparator alike."""
+        blk, a, D, M, G = self.model.blocks[l], self.act[l], self.D, self.M, self.Gr
+        # extras route: dY behind the branch's dropout / drop-path backward, X the dropped hidden activation
+        g2 = self.g2_l[l] if self.g2_l[l] is not None else self.dx_out[l + 1]
+        g1 = self.g1_l[l] if self.g1_l[l] is not None else self.dx_mid[l]
+        fc2 = (g2.view(M, D), a["hd"] if a["hd"] is not None else a["h"], G(blk.mlp.fc2.weight), G(blk.mlp.fc2.bias))
+        proj = (g1.view(M, D), a["a"].view(M, D), G(blk.attn.proj.weight), G(blk.attn.proj.bias))
+        if self.recompute_ln:   # X operands LayerNorm2(x_mid) / LayerNorm1(x_in): re-normalised inside the kernel
+            fc1 = (self.du_l[l], a["xmid"].view(M, D), G(blk.mlp.fc1.weight), G(blk.mlp.fc1.bias),
+                   (a["m2"], a["r2"], blk.norm2.weight.data, blk.norm2.bias.data))
+            qkv = (self.dqkv_l[l].view(M, 3 * D), self.x[l].view(M, D), G(blk.attn.qkv.weight), None,
+                   (a["m1"], a["r1"], blk.norm1.weight.data, blk.norm1.bias.data))
+        else:
+            fc1 = (self.du_l[l], a["xn2"].view(M, D), G(blk.mlp.fc1.weight), G(blk.mlp.fc1.bias))
+            bq = blk.attn.qkv.bias   # (extras route only)
+            qkv = (self.dqkv_l[l].view(M, 3 * D), a["xn1"].view(M, D), G(blk.attn.qkv.weight), None if bq is None else G(bq))
+        if self._top_cls(l):   # their dY is zero outside the class rows: contract over rows b * N only (row step N)
+            fc2, fc1, proj = ((p + (None,) * (5 - len(p)) + (self.N,)) for p in (fc2, fc1, proj))
+        return dict(fc2=fc2, fc1=fc1, proj=proj, qkv=qkv)
+
+    def _embed_wgrad(self):
+        mdl, G = self.model, self.Gr
+        return (self.dpatch, self.patches, G(mdl.patch_embed.weight).view(self.D, -1), G(mdl.patch_embed.bias))
+
+    def _part_layers(self, part):
+        """(hi, lo) of part "all" | "upper" (head + layers L-1..split) | "lower" (layers split-1..0 + patch embed)."""
+        top, split = self.Lyr - 1, self.split_layer
+        return {"all": (top, 0), "upper": (top, split), "lower": (split - 1, 0)}[part]
 
     def _wgrad_group(self, part):
         """All weight gradients of `part` in one grouped launch (csrc/wgrad.hip) after the data-gradient chain:
         their operands sit in per-layer buffers, so nothing forces them into the chain, and one launch over
         24+ problems needs ~10x fewer atomically-combined partial blocks than 24 launches."""
         if part not in self._wg_groups:
-            hi, lo = self.Lyr - 1, 0
-            if part == "upper":
-                lo = self.split_layer
-            elif part == "lower":
-                hi = self.split_layer - 1
-            probs = self._wgrad_problems(lo, hi, part != "upper")
+            hi, lo = self._part_layers(part)
+            probs = [p for l in range(hi, lo - 1, -1) for p in self._wgrad_problems(l).values()]
+            if part != "upper":
+                probs.append(self._embed_wgrad())
             # lists above the kernel-argument limit (ViT-B/16: 49 problems) go out as equal launches (25 + 24, not 28 + 21:
             # the placement of blocks over the chip works per launch)
             ng = -(-len(probs) // K.WgradGroup.MAX)
@@ -784,80 +706,29 @@ class TrainEngine:
         for grp in self._wg_groups[part]:
             grp.launch()
 
-    def _wgrad(self, fn):
-        """One weight-gradient GEMM per nn.Linear (VITPE_GROUP_WGRAD=0); the default leaves them to _wgrad_group."""
+    def _gemm_tn(self, l, name):
+        """Layer l's weight gradient `name` as its own GEMM at this point of the chain (VITPE_GROUP_WGRAD=0); the default
+        leaves it to _wgrad_group."""
         if not self.group_wgrad:
-            fn()
+            K.gemm_tn(*self._wgrad_problems(l)[name])
 
     def _backward(self, part="all"):
         """part: "all" | "upper" (head + layers L-1..split) | "lower" (layers split-1..0 + patch embed)."""
-        mdl, B, N, D, M = self.model, self.B, self.N, self.D, self.M
-        G = self.Gr
-        hi, lo = self.Lyr - 1, 0
-        if part == "upper":
-            lo = self.split_layer
-        elif part == "lower":
-            hi = self.split_layer - 1
+        mdl, G = self.model, self.Gr
+        hi, lo = self._part_layers(part)
         if part != "lower" and not self.fuse_head:
-            dxL = self.dx_out[self.Lyr]
-            K.head_bwd(self.dlogits, mdl.head.weight.data, mdl.norm.weight.data, self.head_ws, self.T, N,
-                       G(mdl.head.weight), G(mdl.head.bias), G(mdl.norm.weight), G(mdl.norm.bias), dx=dxL,
+            K.head_bwd(self.dlogits, mdl.head.weight.data, mdl.norm.weight.data, self.head_ws, self.T, self.N,
+                       G(mdl.head.weight), G(mdl.head.bias), G(mdl.norm.weight), G(mdl.norm.bias), dx=self.dx_out[self.Lyr],
                        ws_dyn=self.ws_dyn)
         for l in range(hi, lo - 1, -1):
-            if self.extras:
-                self._extras_layer_bwd(l)
-                continue
-            blk, a = mdl.blocks[l], self.act[l]
-            dy3, dmid3, du, dqkv = self.dx_out[l + 1], self.dx_mid[l], self.du_l[l], self.dqkv_l[l]
-            dy = dy3.view(M, D)
-            # ---- MLP branch: x_out = xmid + fc2(gelu(fc1(LN2(xmid))))
-            self._wgrad(lambda: K.gemm_tn(dy, a["h"], G(blk.mlp.fc2.weight), G(blk.mlp.fc2.bias)))
-            fc1_wgrad = lambda: K.gemm_tn(du, a["xn2"].view(M, D), G(blk.mlp.fc1.weight), G(blk.mlp.fc1.bias))  # noqa: E731
-            tail_done = False
-            if self.tail2:   # gelu' + both data gradients + LayerNorm2 backward + residual + the projection's data gradient
-                self._block_tail_bwd(l, blk, a, pre=(self.fuse_lnbwd and self.group_wgrad and l < hi))   # (+ block l + 1's qkv data gradient;
-                # per-GEMM weight gradients would read dy before the fused kernel has written it)
-                self._wgrad(fc1_wgrad)
-                tail_done = True
-            else:
-                K.linear(dy, self.St(blk.mlp.fc2.weight), None, epi=L.EPI_GELU_BWD, u=a["u"], out=du)
-                self._wgrad(fc1_wgrad)
-                if self.fuse_ln_bwd:   # data gradient of fc1 + LayerNorm2 backward + residual add in one kernel
-                    K.linear_lnbwd(du, self.St(blk.mlp.fc1.weight), a["xmid"].view(M, D), a["m2"], a["r2"],
-                                   blk.norm2.weight.data, dy, G(blk.norm2.weight), G(blk.norm2.bias),
-                                   out=dmid3.view(M, D))
-                else:
-                    K.linear(du, self.St(blk.mlp.fc1.weight), None, out=self.dtmp.view(M, D))
-                    K.layernorm_bwd(self.dtmp, a["xmid"], a["m2"], a["r2"], blk.norm2.weight.data, G(blk.norm2.weight),
-                                    G(blk.norm2.bias), dres=dy3, out=dmid3, workspace=self.ln_ws)
-            # ---- attention branch: xmid = x_in + proj(attn(LN1(x_in)))
-            dm = dmid3.view(M, D)
-            self._wgrad(lambda: K.gemm_tn(dm, a["a"].view(M, D), G(blk.attn.proj.weight), G(blk.attn.proj.bias)))
-            if not tail_done:
-                K.linear(dm, self.St(blk.attn.proj.weight), None, out=self.dtmp.view(M, D))
-            self._attn_bwd(l, self.da_top if self._top_cls(l) else self.dtmp)
-            self._wgrad(lambda: K.gemm_tn(dqkv.view(M, 3 * D), a["xn1"].view(M, D), G(blk.attn.qkv.weight), None))
-            if self.fuse_lnbwd and self.group_wgrad and l > lo:
-                pass   # runs as the prologue of block l - 1's tail backward (next iteration)
-            elif self.fuse_ln_bwd and self.lnbwd2:   # ... on the wave-per-tile mapping, packed qkv.weight^T
-                K.linear_lnbwd2(dqkv.view(M, 3 * D), self.Frt(blk.attn.qkv.weight), self.x[l].view(M, D), a["m1"],
-                                a["r1"], blk.norm1.weight.data, dm, G(blk.norm1.weight), G(blk.norm1.bias),
-                                out=self.dx_out[l].view(M, D))
-            elif self.fuse_ln_bwd:   # data gradient of qkv + LayerNorm1 backward + residual add in one kernel
-                K.linear_lnbwd(dqkv.view(M, 3 * D), self.St(blk.attn.qkv.weight), self.x[l].view(M, D), a["m1"],
-                               a["r1"], blk.norm1.weight.data, dm, G(blk.norm1.weight), G(blk.norm1.bias),
-                               out=self.dx_out[l].view(M, D))
-            else:
-                K.linear(dqkv.view(M, 3 * D), self.St(blk.attn.qkv.weight), None, out=self.dtmp.view(M, D))
-                K.layernorm_bwd(self.dtmp, self.x[l], a["m1"], a["r1"], blk.norm1.weight.data, G(blk.norm1.weight),
-                                G(blk.norm1.bias), dres=dmid3, out=self.dx_out[l], workspace=self.ln_ws)
+            self._layer_bwd(l, lo, hi)
         if part != "upper":
             dape = None
             if isinstance(mdl.pos_embed, AbsolutePositionalEncoding):
                 dape = G(mdl.pos_embed.pos_embed)[0, :self.P]
             K.embed_bwd(self.dx_out[0], G(mdl.cls_token).view(-1), dape, out=self.dpatch)
             if not self.group_wgrad:
-                K.gemm_tn(self.dpatch, self.patches, G(mdl.patch_embed.weight).view(D, -1), G(mdl.patch_embed.bias))
+                K.gemm_tn(*self._embed_wgrad())
         if self.group_wgrad:
             self._wgrad_group(part)
 
@@ -865,7 +736,7 @@ class TrainEngine:
         clip = self.clip_max_norm is not None
         if clip:   # after every all-reduce in every step shape: all ranks reduce the same flat_g to the same coefficient
             K.grad_clip(self.flat_g, self.hp, self._clip_partial)
-        K.adamw_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.hp, shadow_bf16=self.flat_s, ticked=getattr(self, "_ticked", False),
+        K.adamw_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.hp, shadow_bf16=self.flat_s, ticked=self._ticked,
                      zero_grad=True, clipped=clip)
         self._ticked = False
         self.refresh_shadows(cast_flat=False)
@@ -983,7 +854,7 @@ class TrainEngine:
             if self.batch_idx is None:
                 self.batch_idx = torch.zeros(self.B, dtype=torch.int64, device=self.dev)
         self.dataset = dataset
-        self.graph_fb = self.graph_fb2 = self.graph_opt = None
+        self._drop_graphs()
 
     def _load_indices(self, idx: torch.Tensor, dataset=None):
         """Sample indices of the next batch: [n] int64 with n <= B; a short (ragged last) batch is padded by repeating
@@ -1185,14 +1056,8 @@ class TrainEngine:
                                    fns=[tail_bp(l) for l in range(self.Lyr - 1)], flop=tail_flop + 2 * M * D * 3 * D,
                                    bytes=self._tail_bytes(fwd=False) + (3 * M * D + 2 * M * D) * es))
             if self.lnbwd2:
-                def dg(l):
-                    blk, a = mdl.blocks[l], self.act[l]
-                    return lambda: K.linear_lnbwd2(self.dqkv_l[l].view(M, 3 * D), self.Frt(blk.attn.qkv.weight),
-                                                   self.x[l].view(M, D), a["m1"], a["r1"], blk.norm1.weight.data,
-                                                   self.dx_mid[l].view(M, D), self.Gr(blk.norm1.weight), self.Gr(blk.norm1.bias),
-                                                   out=self.dx_out[l].view(M, D))
                 probes.append(dict(name="dgrad_qkv_ln1_bwd", kernel="ln_bwd2_kernel (dgrad qkv + LayerNorm1 backward + residual)",
-                                   fns=[dg(l) for l in range(self.Lyr)], flop=2 * M * D * 3 * D,
+                                   fns=[(lambda l=l: self._qkv_bwd(l)) for l in range(self.Lyr)], flop=2 * M * D * 3 * D,
                                    bytes=(3 * M * D + 3 * M * D) * es))     # d_qkv, x, d x_mid in; d x out
             self._wgrad_group("all") if "all" not in self._wg_groups else None
             wg_flop = sum(2 * dy.shape[0] * dy.shape[1] * x.shape[1] for grp in self._wg_groups["all"] for dy, x, _, _ in grp.keep)
@@ -1206,11 +1071,10 @@ class TrainEngine:
         rank's part of the batch mean, reference train.py:146-149; n_global defaults to n), acc[1] += #correct.
         Device-side; leaves the training scalars untouched."""
         key = (n, n_global or n)
-        if getattr(self, "_eval_ctl_key", None) != key:   # (one host -> device copy per distinct batch shape, not per batch)
+        if self._eval_ctl_key != key:   # (one host -> device copy per distinct batch shape, not per batch)
             self._eval_ctl = torch.tensor([0.0, 1.0 / max(n_global or n, 1), float(n), 0.0], device=self.dev)
             self._eval_ctl_key = key
-        ctl = self._eval_ctl
-        K.cross_entropy_ctl(self.logits, self.labels, ctl, dlogits=None, out2=self.out2, metric_acc=acc)
+        K.cross_entropy_ctl(self.logits, self.labels, self._eval_ctl, dlogits=None, out2=self.out2, metric_acc=acc)
 
     def read_metrics(self, reset=True):
         """(sum over the steps since the last read of the global-batch mean loss, #correct over all ranks) -- the
