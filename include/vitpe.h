@@ -373,8 +373,6 @@ int vitpe_layernorm_bwd(int dtype, const void* dy, const void* x, const float* m
                         const float* rstd, const float* gamma, const void* dres, void* dx,
                         float* dgamma, float* dbeta, float* workspace, int M, int D,
                         vitpe_stream_t stream);
-int vitpe_reduce_partials(const float* partial, int nparts, int len0, int len1, float* dst0,
-                          float* dst1, vitpe_stream_t stream);
 
 /* ---- transforms.Resize (train.py:69-70,78-79) -------------------------------------------------
  * Resize(S) on the square uint8 images of datasets.MNIST (mode L) / datasets.CIFAR10 (mode RGB) is PIL's
@@ -489,17 +487,6 @@ int vitpe_head_bwd(int dtype, const float* dlogits, const float* Wh, const float
                    const float* ws_xhat, const float* ws_yn, const float* ws_rstd, float* ws_dyn,
                    void* dx, float* dWh, float* dbh, float* dgamma, float* dbeta, int B, int Ntok,
                    int D, int Cn, vitpe_stream_t stream);
-/* Training-step fusion of vitpe_head_fwd + vitpe_cross_entropy + vitpe_head_bwd (vit.py:284-285, train.py:113-114
- * and their autograd) for classes <= 64 (else hipErrorNotSupported): logits, dlogits = (softmax - onehot) *
- * grad_scale, dx (class row; other rows zero), out2 = [mean loss, #correct] of THIS batch, metric_acc (nullable)
- * += out2, parameter gradients accumulated.  scratch: 4 zero-initialised floats owned by the caller (batch
- * totals + arrival counter; the kernel re-arms it, so graph replay needs no memset).                      */
-int vitpe_head_loss(int dtype, const void* x, const float* gamma, const float* beta, const float* Wh,
-                    const float* bh, const long long* labels, float* logits, float* dlogits, float* ws_xhat,
-                    float* ws_yn, float* ws_dyn, void* dx, float* out2, float* metric_acc, float* scratch,
-                    float* dWh, float* dbh, float* dgamma, float* dbeta, int B, int Ntok, int D, int Cn,
-                    float eps, float grad_scale, vitpe_stream_t stream);
-
 /* The train step's head: vitpe_head_fwd + vitpe_cross_entropy_ctl + vitpe_head_bwd in one launch pair (classes <= 64,
  * D <= 768, else hipErrorNotSupported).  ctl as vitpe_cross_entropy_ctl.  dx: ONLY the class rows are written -- the
  * caller keeps rows 1.. of every image zero (they never change).  per_image: [B,2] work buffer ((loss, correct) per

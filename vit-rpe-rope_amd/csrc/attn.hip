@@ -1459,16 +1459,3 @@ extern "C" int vitpe_debug_attn_census(const void* xn, const void* wqkv, void* o
   hipLaunchKernelGGL((attn_fwd_kernel<bf16, 32, 192, 5, KM_ROPE, 65, 2, false, true>), dim3((B + 1) / 2), dim3(768), 0, stream, a);
   VITPE_CHECK_LAUNCH();
 }
-
-// debug: resident workgroups per CU the runtime computes for the main attention instantiations
-extern "C" int vitpe_debug_attn_occupancy(int which) {
-  int n = -1;
-  hipError_t e;
-  if (which == 0)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, attn_fwd_kernel<bf16, 32, 192, 5, KM_ROPE, 65, 2, true>, 768, 0);
-  else if (which == 1)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, attn_fwd_kernel<bf16, 32, 192, 5, KM_PLAIN, 65, 2, true>, 768, 0);
-  else
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, attn_bwd_reg_kernel<32, 192, 5, KM_ROPE, 65, 2, true, false>, 768, 0);
-  return e == hipSuccess ? n : -(int)e;
-}

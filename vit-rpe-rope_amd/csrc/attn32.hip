@@ -119,7 +119,7 @@ VITPE_DEV float swap32_sum(float v) {
 // SIMD drift apart and one's LDS waits and softmax run under another's MFMAs (with s_barrier per chunk the oldest wave
 // of a SIMD spent 6 K of its 14 K k-loop cycles parked: census in DESIGN.md).  The LDS-DMA is issued from inline asm:
 // through the builtin, hipcc waits vmcnt(0) right behind the issue (it cannot tell the ring slots apart).
-template <int KM, bool LNF, bool MIXED, bool CENSUS = false, int EXP = 0>   // EXP: timing experiments of the census build (WRONG results)
+template <int KM, bool LNF, bool MIXED, bool CENSUS = false>
 __global__ __launch_bounds__(768, 3) void attn32_fwd_kernel(AttnArgs a) {
   using C = AttnCfg<bf16, 32, 192, 5, 1, 65>;   // (bias-table helpers of attn_common.h: TABLD = 160, PBLD = 32)
   constexpr int D = W32::D, N = W32::N, LDX = W32::LDX, H = W32::H;
@@ -277,18 +277,14 @@ __global__ __launch_bounds__(768, 3) void attn32_fwd_kernel(AttnArgs a) {
     unsigned long long t0 = 0;
     if (CENSUS) t0 = __builtin_amdgcn_s_memtime();
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    if (EXP & 4) {
-      __builtin_amdgcn_s_barrier();
-    } else if (!(EXP & 2)) {
-      typedef __attribute__((address_space(3))) int lds_int;
-      lds_int* const ctr = (lds_int*)(pflag + h * 8 + k);
-      int seen = 0;
-      if (lane == 0) seen = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // 1: the partner is already here
-      seen = __builtin_amdgcn_readfirstlane(seen);
-      for (int spin = 0; seen < 1 && spin < (1 << 18); ++spin) {        // (bounded: a lost partner must not hang the chip)
-        __builtin_amdgcn_s_sleep(1);
-        seen = __builtin_amdgcn_readfirstlane(*(volatile lds_int*)ctr) - 1;
-      }
+    typedef __attribute__((address_space(3))) int lds_int;
+    lds_int* const ctr = (lds_int*)(pflag + h * 8 + k);
+    int seen = 0;
+    if (lane == 0) seen = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // 1: the partner is already here
+    seen = __builtin_amdgcn_readfirstlane(seen);
+    for (int spin = 0; seen < 1 && spin < (1 << 18); ++spin) {        // (bounded: a lost partner must not hang the chip)
+      __builtin_amdgcn_s_sleep(1);
+      seen = __builtin_amdgcn_readfirstlane(*(volatile lds_int*)ctr) - 1;
     }
     asm volatile("" ::: "memory");
     if (CENSUS) t_bar += __builtin_amdgcn_s_memtime() - t0;
@@ -316,11 +312,9 @@ __global__ __launch_bounds__(768, 3) void attn32_fwd_kernel(AttnArgs a) {
                  wo2 = ldsfrag(wbuf + (BUF) * PBUF + ooff[2]);                                                      \
     pair_sync(C);                                                                                                   \
     if ((C) + 2 < 6) dma_chunk((C) + 2, (BUF));                                                                     \
-    if (!(EXP & 1)) {                                                                                               \
-      od[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wo0, xo, od[0], 0, 0, 0);                                     \
-      od[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wo1, xo, od[1], 0, 0, 0);                                     \
-      od[2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wo2, xo, od[2], 0, 0, 0);                                     \
-    }                                                                                                               \
+    od[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wo0, xo, od[0], 0, 0, 0);                                       \
+    od[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wo1, xo, od[1], 0, 0, 0);                                       \
+    od[2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wo2, xo, od[2], 0, 0, 0);                                       \
     VITPE_A32_FENCE                                                                                                 \
     xa = ldsfrag(xp + (XO) + 32); xb = ldsfrag(xp + (XO) + 32 + 32 * LDX);   /* (past the last chunk: in-bounds, unused) */ \
     wv = ldsfrag(wp + (1 - (BUF)) * PBUF + 4 * 512); wk = ldsfrag(wp + (1 - (BUF)) * PBUF + 2 * 512);               \
@@ -333,7 +327,7 @@ __global__ __launch_bounds__(768, 3) void attn32_fwd_kernel(AttnArgs a) {
   bf16x8 wv = ldsfrag(wp + 4 * 512), wk = ldsfrag(wp + 2 * 512), wq = ldsfrag(wp + 0 * 512);
   // matrix-pipe-bound phase at raised priority: once the oldest wave of a SIMD is in its (VALU-bound) softmax, the younger
   // waves' MFMAs must still win the issue port -- the softmax fills the 24 free issue cycles of every 32-cycle MFMA
-  if (!(EXP & 8)) __builtin_amdgcn_s_setprio(2);
+  __builtin_amdgcn_s_setprio(2);
 #pragma unroll 1
   for (int cp = 0; cp < 3; ++cp) {
     VITPE_A32_CHUNK(2 * cp, 0, 0)
@@ -349,7 +343,7 @@ __global__ __launch_bounds__(768, 3) void attn32_fwd_kernel(AttnArgs a) {
     for (int t = 0; t < 3; ++t) *reinterpret_cast<f32x4*>(&odd_raw[oc * 3 * D + 16 * ((h * 3 + t) * 2 + img) + 4 * og]) = od[t];
   }
   pair_sync(6);   // the odd token's rows are published to the partner
-  if (!(EXP & 8)) __builtin_amdgcn_s_setprio(0);
+  __builtin_amdgcn_s_setprio(0);
   auto write_xn_out = [&]() {
     // LayerNorm(x) for the backward pass, from the LDS image AFTER the k-loop: stored from the staging phase the 12.8 MB
     // sat in front of every LDS-DMA piece in the in-order vmcnt queue, and the first handshakes waited for HBM writes
@@ -689,16 +683,11 @@ extern "C" int vitpe_fused_attention_fwd_wide(int dtype, const void* x, const fl
 // s_memtime at 0 start, 1 staged, 2 barrier passed, 3 k-loop done, 4 operand fragments built, 5 patch queries done, 6 end;
 // 8 = cycles inside the k-loop's barriers (incl. the LDS-DMA wait), 9 / 10 = s_memrealtime (100 MHz, chip-wide) at start / end
 extern "C" int vitpe_debug_attn32_census(const void* xn, const void* wqkv_wide, void* out, const float* cos,
-                                         const float* sin, int B, unsigned long long* census, int exp, hipStream_t stream) {
+                                         const float* sin, int B, unsigned long long* census, hipStream_t stream) {
   VITPE_REQUIRE(xn && wqkv_wide && out && cos && sin && census && B > 0);
   AttnArgs a = attn_args({PE_ROPE_AXIAL, cos, sin, nullptr, nullptr, 8, 0, 0}, B, 65, 0, 32);
   a.xn = xn; a.wqkv = wqkv_wide; a.out = out; a.census = census;
   const dim3 grid((B + 1) / 2), block(768);
-  if (exp == 1) hipLaunchKernelGGL((attn32_fwd_kernel<KM_ROPE, false, false, true, 1>), grid, block, 0, stream, a);
-  else if (exp == 2) hipLaunchKernelGGL((attn32_fwd_kernel<KM_ROPE, false, false, true, 2>), grid, block, 0, stream, a);
-  else if (exp == 3) hipLaunchKernelGGL((attn32_fwd_kernel<KM_ROPE, false, false, true, 3>), grid, block, 0, stream, a);
-  else if (exp == 4) hipLaunchKernelGGL((attn32_fwd_kernel<KM_ROPE, false, false, true, 4>), grid, block, 0, stream, a);
-  else if (exp == 8) hipLaunchKernelGGL((attn32_fwd_kernel<KM_ROPE, false, false, true, 8>), grid, block, 0, stream, a);
-  else hipLaunchKernelGGL((attn32_fwd_kernel<KM_ROPE, false, false, true>), grid, block, 0, stream, a);
+  hipLaunchKernelGGL((attn32_fwd_kernel<KM_ROPE, false, false, true>), grid, block, 0, stream, a);
   VITPE_CHECK_LAUNCH();
 }

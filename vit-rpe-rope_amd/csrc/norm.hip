@@ -303,39 +303,9 @@ __global__ __launch_bounds__(1024) void ln_bwd32_kernel(const bf16* __restrict__
   }
 }
 
-// dst0[i] += sum_p partial[p][i] (i < len0) ; dst1[i-len0] += ... (len0 <= i < len0+len1)
-__global__ void reduce_partials_kernel(const float* __restrict__ partial, int nparts, int len0, int len1,
-                                       float* __restrict__ dst0, float* __restrict__ dst1) {
-  // block = 32 columns x 8 partial-groups; LDS tree over the groups (fixed order)
-  __shared__ float red[8][33];
-  const int len = len0 + len1;
-  const int i = blockIdx.x * 32 + (threadIdx.x & 31), grp = threadIdx.x >> 5;
-  float s = 0.f;
-  if (i < len)
-    for (int p = grp; p < nparts; p += 8) s += partial[(size_t)p * len + i];
-  red[grp][threadIdx.x & 31] = s;
-  __syncthreads();
-  if (grp == 0 && i < len) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) t += red[k][threadIdx.x];
-    if (i < len0) dst0[i] += t; else dst1[i - len0] += t;
-  }
-}
-
 }  // namespace vitpe
 
 using namespace vitpe;
-
-extern "C" int vitpe_reduce_partials(const float* partial, int nparts, int len0, int len1, float* dst0,
-                                     float* dst1, hipStream_t stream) {
-  VITPE_REQUIRE(partial && dst0 && nparts >= 0 && len0 >= 0 && len1 >= 0 && (len1 == 0 || dst1));
-  const int len = len0 + len1;
-  if (len == 0) return 0;
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3((len + 31) / 32), dim3(256), 0, stream, partial, nparts,
-                     len0, len1, dst0, dst1);
-  VITPE_CHECK_LAUNCH();
-}
 
 static inline bool ln_dims_ok(int dtype, int D) {
   const int chn = dtype == 1 ? 8 : 4;

@@ -225,7 +225,7 @@ VITPE_DEV void t2_gelu(float x, float& h, float& g) {
 // The three are independent, so they go into ONE scheduling region: the two products' fragments alternate through one
 // ring of R registers and every MFMA is followed by NV VALU instructions of the epilogue.
 // w1f / w2f: lane-offset LDS pointers to the sub-chunk's fragments (fc1: (tile * 6 + k step) * 512, fc2: tile * 512).
-template <bool F1, bool F2, int NV, int EXP, int R = 8, class GFn>
+template <bool F1, bool F2, int NV, int R = 8, class GFn>
 VITPE_DEV void t2_step(const bf16* w1f, const bf16* w2f, const Frag<bf16> (&bf)[T2_KS], f32x4 (&a1n)[2],
                        const Frag<bf16>& hprev, f32x4 (&acc2)[T2_NT], GFn gfn) {
   constexpr int TOT = (F1 ? 12 : 0) + (F2 ? 12 : 0);
@@ -239,10 +239,10 @@ VITPE_DEV void t2_step(const bf16* w1f, const bf16* w2f, const Frag<bf16> (&bf)[
     };
     Frag<bf16> w[R];
 #pragma unroll
-    for (int i = 0; i < R - 1; ++i) w[i] = ld_frag(frag_ptr((EXP & 1) ? (i & ~3) : i));
+    for (int i = 0; i < R - 1; ++i) w[i] = ld_frag(frag_ptr(i));
 #pragma unroll
     for (int q = 0; q < TOT; ++q) {
-      if (q + R - 1 < TOT) w[(q + R - 1) % R] = ld_frag(frag_ptr((EXP & 1) ? ((q + R - 1) & ~3) : q + R - 1));
+      if (q + R - 1 < TOT) w[(q + R - 1) % R] = ld_frag(frag_ptr(q + R - 1));
       const bool is2 = (F1 && F2) ? (q % 2 == 0) : F2;
       const int j = (F1 && F2) ? q / 2 : q;
       if (is2) mma(w[q % R], hprev, acc2[j]);
@@ -263,12 +263,12 @@ VITPE_DEV void t2_step(const bf16* w1f, const bf16* w2f, const Frag<bf16> (&bf)[
 }
 
 // forward: G = GELU of sub-chunk t (a1c = u with bias -> h fragment hnew; SAVE: h and g' rows stored)
-template <bool F1, bool G, bool F2, bool SAVE, int EXP = 0>
+template <bool F1, bool G, bool F2, bool SAVE>
 VITPE_DEV void t2_substep(const bf16* w1f, const bf16* w2f, const Frag<bf16> (&bf)[T2_KS], f32x4 (&a1n)[2],
                           const f32x4 (&a1c)[2], const Frag<bf16>& hprev, Frag<bf16>& hnew, f32x4 (&acc2)[T2_NT],
                           const T2Row& gpr, const T2Row& hr, int g) {
   constexpr int NV = !G ? 0 : (F1 && F2) ? T2_NV : 2 * T2_NV;
-  t2_step<F1, F2, NV, EXP>(w1f, w2f, bf, a1n, hprev, acc2, [&]() {
+  t2_step<F1, F2, NV>(w1f, w2f, bf, a1n, hprev, acc2, [&]() {
     if (!G) return;
     // scalar fp32 on purpose: packed f32 VALU (v_pk_mul/fma_f32) issues several times slower than two scalar
     // instructions beside MFMAs on gfx950 (MI355X_MICROARCH.md, issue-cost table), and this epilogue IS the bound
@@ -278,14 +278,13 @@ VITPE_DEV void t2_substep(const bf16* w1f, const bf16* w2f, const Frag<bf16> (&b
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const float x = a1c[q][t];
-        if (EXP & 2) { hh[q][t] = 0.5f * x; gp[q][t] = x; continue; }
         float hv, gv;
         t2_gelu(x, hv, gv);
         hh[q][t] = hv;
         gp[q][t] = gv;
       }
     }
-    if (SAVE && !(EXP & 4)) {
+    if (SAVE) {
       t2_store_pair_f16<T2_AUX_HID>(gpr, 0, g, gp[0], gp[1]);  // read again only in backward; IEEE half (see t2_store_pair_f16)
       t2_store_pair<T2_AUX_HID>(hr, 0, g, hh[0], hh[1]);
     }
@@ -293,7 +292,7 @@ VITPE_DEV void t2_substep(const bf16* w1f, const bf16* w2f, const Frag<bf16> (&b
   });
 }
 
-template <bool SAVE, bool CENSUS, int EXP = 0>
+template <bool SAVE, bool CENSUS>
 __global__ __launch_bounds__(T2F_THREADS) void block_tail2_fwd_kernel(Tail2Args a) {
   using T = bf16;
   constexpr int D = T2_D, NT = T2_NT, KS = T2_KS;
@@ -502,16 +501,16 @@ __global__ __launch_bounds__(T2F_THREADS) void block_tail2_fwd_kernel(Tail2Args 
         const T* wb = sW + ((p + 2) % 3) * T2_SLABF * 512 + lane * 8;
         if (p < nchunk && (p & 1) == half) {
           bias1(aX, 2 * p);
-          t2_substep<true, false, false, SAVE, EXP>(wb, wb, bf, aX, aY, hQ, hQ, acc2, gpr, hr, g);
+          t2_substep<true, false, false, SAVE>(wb, wb, bf, aX, aY, hQ, hQ, acc2, gpr, hr, g);
           bias1(aY, 2 * p + 1);
-          t2_substep<true, true, false, SAVE, EXP>(wb + 2 * KS * 512, wb, bf, aY, aX, hQ, hP, acc2, gpr + 32 * (2 * p),
+          t2_substep<true, true, false, SAVE>(wb + 2 * KS * 512, wb, bf, aY, aX, hQ, hP, acc2, gpr + 32 * (2 * p),
                                                    hr + 32 * (2 * p), g);
-          t2_substep<false, true, false, SAVE, EXP>(wb, wb, bf, aX, aY, hQ, hQ, acc2, gpr + 32 * (2 * p + 1), hr + 32 * (2 * p + 1), g);
+          t2_substep<false, true, false, SAVE>(wb, wb, bf, aX, aY, hQ, hQ, acc2, gpr + 32 * (2 * p + 1), hr + 32 * (2 * p + 1), g);
         } else if (p >= 1 && ((p - 1) & 1) == half) {
           const T* w2b = wb + T2_HALF * 512;
           Frag<T> hdummy;
-          t2_substep<false, false, true, SAVE, EXP>(w2b, w2b, bf, aX, aY, hP, hdummy, acc2, gpr, hr, g);
-          t2_substep<false, false, true, SAVE, EXP>(w2b, w2b + NT * 512, bf, aX, aY, hQ, hdummy, acc2, gpr, hr, g);
+          t2_substep<false, false, true, SAVE>(w2b, w2b, bf, aX, aY, hP, hdummy, acc2, gpr, hr, g);
+          t2_substep<false, false, true, SAVE>(w2b, w2b + NT * 512, bf, aX, aY, hQ, hdummy, acc2, gpr, hr, g);
         }
         signal_done(p + 1);
       }
@@ -543,9 +542,9 @@ __global__ __launch_bounds__(T2F_THREADS) void block_tail2_fwd_kernel(Tail2Args 
       {
         const T* wb = sW + 2 * T2_SLABF * 512 + lane * 8;
         bias1(aX, 0);
-        t2_substep<true, false, false, SAVE, EXP>(wb, wb, bf, aX, aY, hQ, hQ, acc2, gpr, hr, g);                           // F1_0
+        t2_substep<true, false, false, SAVE>(wb, wb, bf, aX, aY, hQ, hQ, acc2, gpr, hr, g);                           // F1_0
         bias1(aY, 1);
-        t2_substep<true, true, false, SAVE, EXP>(wb + 2 * KS * 512, wb, bf, aY, aX, hQ, hP, acc2, gpr, hr, g);             // F1_1 G_0
+        t2_substep<true, true, false, SAVE>(wb + 2 * KS * 512, wb, bf, aY, aX, hQ, hP, acc2, gpr, hr, g);             // F1_1 G_0
         signal_done(1);
       }
       stamp(5);
@@ -557,10 +556,10 @@ __global__ __launch_bounds__(T2F_THREADS) void block_tail2_fwd_kernel(Tail2Args 
           const T* wb = sW + ((p + 2) % 3) * T2_SLABF * 512 + lane * 8;
           const T* w2b = wb + T2_HALF * 512;
           bias1(aX, 2 * p);
-          t2_substep<true, true, true, SAVE, EXP>(wb, w2b, bf, aX, aY, hP, hQ, acc2, gpr + 32 * (2 * p - 1), hr + 32 * (2 * p - 1), g);
+          t2_substep<true, true, true, SAVE>(wb, w2b, bf, aX, aY, hP, hQ, acc2, gpr + 32 * (2 * p - 1), hr + 32 * (2 * p - 1), g);
           if (CENSUS) { const unsigned long long t = now(); acc_fc1 += t - tm0; tm0 = t; }
           bias1(aY, 2 * p + 1);
-          t2_substep<true, true, true, SAVE, EXP>(wb + 2 * KS * 512, w2b + NT * 512, bf, aY, aX, hQ, hP, acc2, gpr + 32 * (2 * p),
+          t2_substep<true, true, true, SAVE>(wb + 2 * KS * 512, w2b + NT * 512, bf, aY, aX, hQ, hP, acc2, gpr + 32 * (2 * p),
                                              hr + 32 * (2 * p), g);
           signal_done(p + 1);
           if (CENSUS) acc_mix += now() - tm0;
@@ -576,8 +575,8 @@ __global__ __launch_bounds__(T2F_THREADS) void block_tail2_fwd_kernel(Tail2Args 
       {
         const T* w2b = sW + ((nchunk + 2) % 3) * T2_SLABF * 512 + T2_HALF * 512 + lane * 8;
         const int tl = 2 * nchunk - 1;
-        t2_substep<false, true, true, SAVE, EXP>(w2b, w2b, bf, aX, aY, hP, hQ, acc2, gpr + 32 * tl, hr + 32 * tl, g);        // G_last F2
-        t2_substep<false, false, true, SAVE, EXP>(w2b, w2b + NT * 512, bf, aX, aY, hQ, hQ, acc2, gpr, hr, g);               // F2_last
+        t2_substep<false, true, true, SAVE>(w2b, w2b, bf, aX, aY, hP, hQ, acc2, gpr + 32 * tl, hr + 32 * tl, g);        // G_last F2
+        t2_substep<false, false, true, SAVE>(w2b, w2b + NT * 512, bf, aX, aY, hQ, hQ, acc2, gpr, hr, g);               // F2_last
       }
     }
     stamp(8);
@@ -949,9 +948,9 @@ __global__ __launch_bounds__(T2_THREADS) void block_tail2_bwd_kernel(Tail2BwdArg
   {
     const T* wb = slab_ptr(Q);
     aX[0] = z4; aX[1] = z4;
-    t2_step<true, false, 0, 0, RB>(wb, wb, bf, aX, hQ, acc2, [&]() {});                                             // F1_0
+    t2_step<true, false, 0, RB>(wb, wb, bf, aX, hQ, acc2, [&]() {});                                             // F1_0
     aY[0] = z4; aY[1] = z4;
-    t2_step<true, false, 2 * NVB, 0, RB>(wb + 2 * KS * 512, wb, bf, aY, hQ, acc2, [&]() { gstage(aX, gq[0], 0, hP); });   // F1_1 G_0
+    t2_step<true, false, 2 * NVB, RB>(wb + 2 * KS * 512, wb, bf, aY, hQ, acc2, [&]() { gstage(aX, gq[0], 0, hP); });   // F1_1 G_0
     signal_done(Q + 1);
   }
   for (int p = 1; p < nchunk; ++p) {
@@ -959,17 +958,17 @@ __global__ __launch_bounds__(T2_THREADS) void block_tail2_bwd_kernel(Tail2BwdArg
     const T* wb = slab_ptr(Q + p);
     const T* w2b = wb + T2_HALF * 512;
     aX[0] = z4; aX[1] = z4;
-    t2_step<true, true, NVB, 0, RB>(wb, w2b, bf, aX, hP, acc2, [&]() { gstage(aY, gq[1], 2 * p - 1, hQ); });
+    t2_step<true, true, NVB, RB>(wb, w2b, bf, aX, hP, acc2, [&]() { gstage(aY, gq[1], 2 * p - 1, hQ); });
     aY[0] = z4; aY[1] = z4;
-    t2_step<true, true, NVB, 0, RB>(wb + 2 * KS * 512, w2b + NT * 512, bf, aY, hQ, acc2, [&]() { gstage(aX, gq[0], 2 * p, hP); });
+    t2_step<true, true, NVB, RB>(wb + 2 * KS * 512, w2b + NT * 512, bf, aY, hQ, acc2, [&]() { gstage(aX, gq[0], 2 * p, hP); });
     signal_done(Q + p + 1);
   }
   wait_ready(Q + nchunk);
   {
     const T* w2b = slab_ptr(Q + nchunk) + T2_HALF * 512;
     const int tl = nsub - 1;
-    t2_step<false, true, 2 * NVB, 0, RB>(w2b, w2b, bf, aX, hP, acc2, [&]() { gstage(aY, gq[1], tl, hQ); });
-    t2_step<false, true, 0, 0, RB>(w2b, w2b + NT * 512, bf, aX, hQ, acc2, [&]() {});                                  // F2_last
+    t2_step<false, true, 2 * NVB, RB>(w2b, w2b, bf, aX, hP, acc2, [&]() { gstage(aY, gq[1], tl, hQ); });
+    t2_step<false, true, 0, RB>(w2b, w2b + NT * 512, bf, aX, hQ, acc2, [&]() {});                                  // F2_last
     signal_done(Q + nchunk + 1);
   }
   // ---- LayerNorm2 backward + residual: dx_mid = dy + LayerNorm2'(dxn) ------------------------------------------------------------
@@ -1160,7 +1159,7 @@ static int tail2_launch(int dtype, const void* attn_out, const void* x_in, const
                         const float* gamma, const float* beta, void* x_mid, float* mean2, float* rstd2,
                         void* xn_out, const void* W1_packed, const float* b1, const void* W2_packed,
                         const float* b2, void* gp_out, void* h_out, void* out, float* mean_out, float* rstd_out,
-                        float eps2, float eps_next, int M, int D, int HID, unsigned long long* census, int exp, hipStream_t stream) {
+                        float eps2, float eps_next, int M, int D, int HID, unsigned long long* census, hipStream_t stream) {
   VITPE_REQUIRE(attn_out && x_in && Wp_packed && bp && gamma && beta && x_mid && mean2 && rstd2 && W1_packed && b1 &&
                 W2_packed && b2 && out && M >= 0);
   VITPE_REQUIRE((mean_out == nullptr) == (rstd_out == nullptr) && (gp_out == nullptr) == (h_out == nullptr));
@@ -1179,11 +1178,7 @@ static int tail2_launch(int dtype, const void* attn_out, const void* x_in, const
   a.census = census;
   if (census != nullptr) {
     VITPE_REQUIRE(gp_out != nullptr);
-    if (exp == 1) hipLaunchKernelGGL((block_tail2_fwd_kernel<true, true, 1>), dim3(grid), dim3(T2F_THREADS), 0, stream, a);
-    else if (exp == 2) hipLaunchKernelGGL((block_tail2_fwd_kernel<true, true, 2>), dim3(grid), dim3(T2F_THREADS), 0, stream, a);
-    else if (exp == 4) hipLaunchKernelGGL((block_tail2_fwd_kernel<true, true, 4>), dim3(grid), dim3(T2F_THREADS), 0, stream, a);
-    else if (exp == 7) hipLaunchKernelGGL((block_tail2_fwd_kernel<true, true, 7>), dim3(grid), dim3(T2F_THREADS), 0, stream, a);
-    else hipLaunchKernelGGL((block_tail2_fwd_kernel<true, true>), dim3(grid), dim3(T2F_THREADS), 0, stream, a);
+    hipLaunchKernelGGL((block_tail2_fwd_kernel<true, true>), dim3(grid), dim3(T2F_THREADS), 0, stream, a);
   } else if (gp_out != nullptr) {
     hipLaunchKernelGGL((block_tail2_fwd_kernel<true, false>), dim3(grid), dim3(T2F_THREADS), 0, stream, a);
   } else {
@@ -1198,7 +1193,7 @@ extern "C" int vitpe_block_tail2_fwd(int dtype, const void* attn_out, const void
                                      const float* b2, void* gp_out, void* h_out, void* out, float* mean_out, float* rstd_out,
                                      float eps2, float eps_next, int M, int D, int HID, hipStream_t stream) {
   return tail2_launch(dtype, attn_out, x_in, Wp_packed, bp, gamma, beta, x_mid, mean2, rstd2, xn_out, W1_packed, b1, W2_packed,
-                      b2, gp_out, h_out, out, mean_out, rstd_out, eps2, eps_next, M, D, HID, nullptr, 0, stream);
+                      b2, gp_out, h_out, out, mean_out, rstd_out, eps2, eps_next, M, D, HID, nullptr, stream);
 }
 
 // debug (include/vitpe_debug.h): the training instantiation with s_memtime stamps, census[(workgroup * 9 + wave) * 16 + slot]
@@ -1206,10 +1201,10 @@ extern "C" int vitpe_debug_tail2_census(const void* attn_out, const void* x_in, 
                                         const float* gamma, const float* beta, void* x_mid, float* mean2, float* rstd2,
                                         void* xn_out, const void* W1_packed, const float* b1, const void* W2_packed,
                                         const float* b2, void* gp_out, void* h_out, void* out, float* mean_out,
-                                        float* rstd_out, int M, int HID, unsigned long long* census, int exp, hipStream_t stream) {
+                                        float* rstd_out, int M, int HID, unsigned long long* census, hipStream_t stream) {
   VITPE_REQUIRE(census != nullptr);
   return tail2_launch(1, attn_out, x_in, Wp_packed, bp, gamma, beta, x_mid, mean2, rstd2, xn_out, W1_packed, b1, W2_packed, b2,
-                      gp_out, h_out, out, mean_out, rstd_out, 1e-5f, 1e-5f, M, T2_D, HID, census, exp, stream);
+                      gp_out, h_out, out, mean_out, rstd_out, 1e-5f, 1e-5f, M, T2_D, HID, census, stream);
 }
 
 // Backward of vitpe_block_tail2_fwd w.r.t. its inputs: du [M,HID] (fc1's weight gradient reads it), dx_mid [M,192], da [M,192]
