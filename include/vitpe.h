@@ -502,8 +502,9 @@ int vitpe_head_step(int dtype, const void* x, const float* gamma, const float* b
 /* ---- optimizer + weight shadows (train.py:116,195) ------------------------------------------
  * hp (device, 16 floats): [0]=lr [1]=beta1 [2]=beta2 [3]=eps [4]=weight_decay [5]=step
  * [6]=bias_correction1 [7]=bias_correction2 [8]=grad_scale [9]=effective grad scale (grad_scale * clip_coef)
- * [10]=total_norm [11]=clip_coef [12]=max_norm ([9..11] are written by vitpe_grad_clip, [12] by the host; [13..15]
- * unused).  The step counter lives on the
+ * [10]=total_norm [11]=clip_coef [12]=max_norm ([9..11] are written by vitpe_grad_clip, [12] by the host)
+ * [13]=EMA decay [14]=the step counter [5] when the EMA was switched on ([13], [14] written by the host side, read by
+ * vitpe_ema_update) [15]=the decay d_t vitpe_ema_update used last.  The step counter lives on the
  * device so the call can be replayed from a hipGraph.  zero_grad: bit 0 = clear g after the update,
  * bit 1 = the step counter / bias corrections were already advanced (vitpe_head_step hp_tick),
  * bit 2 = the gradient is scaled by hp[9] instead of hp[8] (after vitpe_grad_clip).  Values 0..3 never read hp[9].  */
@@ -523,6 +524,23 @@ int vitpe_adamw_step(float* p, float* g, float* m, float* v, void* shadow_bf16, 
 int vitpe_grad_clip(const float* g, long long n, float* hp, float* partial, int n_partial, vitpe_stream_t stream);
 /* workgroups (= floats of `partial`) vitpe_grad_clip uses for n elements: min(1024, ceil(n / 4096)); 0 for n <= 0 */
 int vitpe_grad_clip_blocks(long long n);
+/* Exponential moving average of the flat fp32 parameters p [n] into e [n], one launch, elementwise:
+ *   e[i] = fmaf(w, p[i] - e[i], e[i]),  w = 1.0f - d_t                         (all fp32; p is only read)
+ *   d_t  = hp[13]                                                              (warmup == 0)
+ *   d_t  = fminf(hp[13], (1.0f + t) / (10.0f + t)),  t = hp[5] - hp[14]        (warmup != 0: TF's num_updates rule)
+ * hp[5] is AdamW's step counter, already advanced for this step (call it after vitpe_adamw_step); hp[14] its value when
+ * the average was switched on.  hp[5], hp[13], hp[14] are only read; one lane stores d_t to hp[15].  The division is
+ * correctly rounded.  p[i] == e[i] leaves e[i]'s bits (fmaf(w, 0, e) == e): a converged average is a fixed point.
+ * p and e 16-byte aligned (16-byte loads and stores per lane, the n % 4 last elements one lane each; the grid is
+ * vitpe_ema_blocks(n) workgroups of 256, grid-stride).  n == 0 launches nothing (hp[15] keeps its value).
+ * hipErrorInvalidValue for NULL hp, NULL p / e with n > 0, n < 0, or a p / e that is not 16-byte aligned; nothing is
+ * launched then.                                                                                                     */
+int vitpe_ema_update(const float* p, float* e, float* hp, long long n, int warmup, vitpe_stream_t stream);
+/* p[i] <-> e[i] in place; shadow_bf16 (nullable) [i] = bf16 of the NEW p[i], the rounding of vitpe_cast bit for bit.  Two
+ * calls restore every bit.  Alignment, n == 0 and refusals as vitpe_ema_update (shadow_bf16 16-byte aligned too).     */
+int vitpe_ema_swap(float* p, float* e, void* shadow_bf16, long long n, vitpe_stream_t stream);
+/* workgroups the two calls above launch for n elements: min(2048, max(1, ceil((n / 4) / 256))); 0 for n <= 0 */
+int vitpe_ema_blocks(long long n);
 int vitpe_cast(int dtype, const float* src, void* dst, long long n, vitpe_stream_t stream);
 int vitpe_transpose_cast(int dtype, const float* src, void* dst, int R, int C, vitpe_stream_t stream);
 /* every weight shadow of the model in one launch.  desc: device array of ndesc records

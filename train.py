@@ -13,8 +13,9 @@ Additions to the reference CLI: --synthetic (CIFAR/MNIST-shaped random batches g
 device: torchvision and the dataset downloads are unavailable offline), --steps_per_epoch,
 --fp32 (exact-fp32 MFMA instead of the default bf16), --random_crop PAD / --hflip (RandomCrop(img_size, padding=PAD) /
 RandomHorizontalFlip on the training images, drawn inside the embed kernel), --clip_grad MAX_NORM
-(torch.nn.utils.clip_grad_norm_ between backward and the optimizer step, inside the captured step).  --batch_size is the
-GLOBAL batch.
+(torch.nn.utils.clip_grad_norm_ between backward and the optimizer step, inside the captured step), --model_ema DECAY /
+--model_ema_warmup (an exponential moving average of the weights, updated inside the captured step; every epoch also
+evaluates the average and keeps its best checkpoint).  --batch_size is the GLOBAL batch.
 """
 import argparse
 import csv
@@ -73,7 +74,16 @@ def get_args(argv=None):
     parser.add_argument('--hflip', action='store_true', help='RandomHorizontalFlip() on the training images')
     parser.add_argument('--clip_grad', type=float, default=0.0, metavar='MAX_NORM',
                         help='clip_grad_norm_(model.parameters(), MAX_NORM) before every optimizer step (0 = off)')
+    parser.add_argument('--model_ema', type=float, default=0.0, metavar='DECAY',
+                        help='keep an exponential moving average of the weights with this decay, evaluate it every epoch '
+                             'and save its best checkpoint (0 = off)')
+    parser.add_argument('--model_ema_warmup', action='store_true',
+                        help='ramp the decay up as min(DECAY, (1 + t) / (10 + t)) over the optimizer steps t')
     args = parser.parse_args(argv)
+    if not (math.isfinite(args.model_ema) and 0.0 <= args.model_ema < 1.0):
+        parser.error("--model_ema must be 0 (off) or a decay in (0, 1)")
+    if args.model_ema_warmup and args.model_ema == 0.0:
+        parser.error("--model_ema_warmup needs --model_ema DECAY")
     if not (math.isfinite(args.clip_grad) and args.clip_grad >= 0.0):
         parser.error("--clip_grad must be a finite number >= 0")
     if not 0 <= args.random_crop <= args.img_size:
@@ -278,7 +288,8 @@ def main(argv=None):
         timestamp = datetime.now().strftime('%Y%m%d_%H%M%S')
         log_file = f'{args.log_dir}/{args.dataset}_{args.pos_encoding}_{timestamp}.csv'
         with open(log_file, 'w', newline='') as f:
-            csv.writer(f).writerow(['epoch', 'train_loss', 'train_acc', 'test_loss', 'test_acc', 'best_acc'])
+            csv.writer(f).writerow(['epoch', 'train_loss', 'train_acc', 'test_loss', 'test_acc', 'best_acc'] +
+                                   (['ema_test_loss', 'ema_test_acc'] if args.model_ema > 0 else []))
 
     train_loader, test_loader = get_dataset(args, info, per_rank, device, rank, world)
     torch.manual_seed(0)
@@ -294,23 +305,37 @@ def main(argv=None):
     if args.random_crop > 0 or args.hflip:   # training steps only: test() runs forward_indexed, which never augments
         engine.set_augment(args.random_crop, args.hflip)
     engine.set_grad_clip(args.clip_grad)   # 0 = off
+    use_ema = args.model_ema > 0
+    if use_ema:   # after the broadcast: the average starts from the parameters every rank trains
+        engine.set_ema(args.model_ema, warmup=args.model_ema_warmup)
 
     best_acc = 0
+    best_ema_acc = -1.0   # (the first epoch's average is always a checkpoint, also at 0 % on a toy run)
     for epoch in range(args.epochs):
         # CosineAnnealingLR(T_max=epochs), stepped per epoch (reference train.py:196,205)
         engine.set_lr(0.5 * args.lr * (1 + math.cos(math.pi * epoch / args.epochs)))
         train_loss, train_acc = train(engine, train_loader)
         test_loss, test_acc = test(engine, test_loader)
+        ema_cols = []
+        if use_ema:   # the same evaluation with the average swapped in for the weights (every rank: test() all-reduces)
+            with engine.ema_weights():
+                ema_test_loss, ema_test_acc = test(engine, test_loader)
+                if rank == 0 and ema_test_acc > best_ema_acc:   # (inside the context model.state_dict() is the average)
+                    best_ema_acc = ema_test_acc
+                    torch.save(model.state_dict(), f'{args.ckpt_dir}/{args.dataset}_{args.pos_encoding}_best_ema.pth')
+            ema_cols = [ema_test_loss, ema_test_acc]
         if rank == 0:
             print(f'\nEpoch: {epoch + 1}/{args.epochs}')
             if test_acc > best_acc:
                 best_acc = test_acc
                 torch.save(model.state_dict(), f'{args.ckpt_dir}/{args.dataset}_{args.pos_encoding}_best.pth')
             with open(log_file, 'a', newline='') as f:
-                csv.writer(f).writerow([epoch + 1, train_loss, train_acc, test_loss, test_acc, best_acc])
+                csv.writer(f).writerow([epoch + 1, train_loss, train_acc, test_loss, test_acc, best_acc] + ema_cols)
             print(f'Train Loss: {train_loss:.4f}, Train Acc: {train_acc:.2f}%')
             print(f'Test Loss: {test_loss:.4f}, Test Acc: {test_acc:.2f}%')
             print(f'Best Test Acc: {best_acc:.2f}%')
+            if use_ema:
+                print(f'EMA Test Loss: {ema_test_loss:.4f}, EMA Test Acc: {ema_test_acc:.2f}%')
     if world > 1:
         torch.distributed.destroy_process_group()
 

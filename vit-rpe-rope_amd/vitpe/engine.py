@@ -14,6 +14,7 @@
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import math
 import os
@@ -80,6 +81,10 @@ class TrainEngine:
     # defaults of the two attributes set_grad_clip() / grad_norm() read, so that they answer on an object that never ran
     # __init__ (tests/test_grad_clip_cpu.py checks their argument handling without a device); __init__ sets both
     clip_max_norm = _clip_partial = None
+    # likewise what set_ema() reads (tests/test_ema_cpu.py): the decay (None = off), the average's flat buffer, the warm-up
+    # switch, and whether ema_weights() currently has the average swapped into flat_p
+    ema_decay = flat_e = None
+    ema_warmup = _ema_swapped = False
 
     def __init__(self, model: VisionTransformer, batch_size: int, compute_dtype=torch.bfloat16, lr=1e-3,
                  weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, process_group=None, use_graph=True, fuse_ln=None,
@@ -116,6 +121,8 @@ class TrainEngine:
         self._ticked = False                               # _loss(tick=True) on the fused head advanced the step counter
         self._eval_ctl = self._eval_ctl_key = None         # eval_loss's scalars, per distinct batch shape
         self.clip_max_norm = self._clip_partial = None     # set_grad_clip(): None = clipping off; the clip's work buffer
+        self.ema_decay = self.flat_e = None                # set_ema(): None = no average kept
+        self.ema_warmup = self._ema_swapped = False
         self._build_flat(lr, weight_decay, betas, eps)
         self._build_buffers()
         self._build_rng_table()
@@ -290,6 +297,107 @@ class TrainEngine:
         if (new is None) != (self.clip_max_norm is None):
             self._drop_graphs()
         self.clip_max_norm = new
+
+    # ---------------------------------------------------------------- weight EMA
+    @staticmethod
+    def _ema_value(decay) -> Optional[float]:
+        """set_ema's decay argument as the engine keeps it: None for None / 0 (off), the float for 0 < decay < 1;
+        VitpeError for anything else."""
+        value = 0.0 if decay is None else float(decay)
+        if not (math.isfinite(value) and 0.0 <= value < 1.0):
+            raise L.VitpeError(f"set_ema: decay must be None, 0 or a number in (0, 1), got {decay!r}")
+        return value if value > 0.0 else None
+
+    def _ema_guard(self, what):
+        if self._ema_swapped:
+            raise L.VitpeError(f"{what}: not available inside ema_weights() (the parameters are swapped with their average; "
+                               f"leave the context first)")
+
+    def _ema_needs_on(self, what):
+        if self.ema_decay is None:
+            raise L.VitpeError(f"{what}: the weight EMA is off (set_ema(decay) first)")
+
+    def set_ema(self, decay: Optional[float], warmup: bool = False):
+        """Keep an exponential moving average of the parameters, updated inside the step right after AdamW (DESIGN.md,
+        "Weight EMA"): flat_e += (1 - d_t) * (flat_p - flat_e), with d_t = decay, or with warmup=True
+        min(decay, (1 + t) / (10 + t)) at t = optimizer steps since the average was switched on (TF's num_updates rule).
+        None or 0 switches it off (the default) and frees the buffer.  Switching on allocates flat_e (4 * n_flat bytes),
+        starts it as a copy of the parameters and drops the captured graphs, as do switching off and changing `warmup`; a
+        new decay for an enabled average is one device write (hp[13]) and keeps them.  Configuration-adjacent state like
+        rng_table: not part of model.state_dict() -- ema_state_dict() / load_ema_state_dict() carry it.  Evaluate on the
+        average inside ema_weights().  Values outside [0, 1) raise VitpeError."""
+        self._ema_guard("set_ema")
+        new = self._ema_value(decay)
+        warmup = bool(warmup) and new is not None
+        if new is not None:
+            self.hp[13] = new
+            if self.ema_decay is None:
+                self.flat_e = torch.empty_like(self.flat_p)
+                self._ema_rebase()
+        else:
+            self.flat_e = None
+        if (new is None) != (self.ema_decay is None) or warmup != self.ema_warmup:
+            self._drop_graphs()
+        self.ema_decay, self.ema_warmup = new, warmup
+
+    def _ema_rebase(self):
+        """The average starts over from the parameters, its warm-up from now: hp[14] = hp[5], device to device."""
+        self.flat_e.copy_(self.flat_p)
+        self.hp[14:15].copy_(self.hp[5:6])
+
+    def reset_ema(self):
+        """Restart the average as a copy of the current parameters (after loading or broadcasting parameters); captured
+        graphs stay valid."""
+        self._ema_guard("reset_ema")
+        self._ema_needs_on("reset_ema")
+        self._ema_rebase()
+
+    def _ema_swap(self):
+        K.ema_swap(self.flat_p, self.flat_e, self.flat_s)
+        self.refresh_shadows(cast_flat=False)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the model IS its average: flat_p and flat_e are exchanged in place (flat_s follows under
+        bf16) and the packed shadows re-derived, so forward_indexed, forward_only, eval_loss, model(images) and
+        model.state_dict() all see the averaged weights -- no second set of shadows exists.  Leaving (also by an exception)
+        exchanges them back: flat_p, flat_e, flat_s and the shadows return bit for bit, no pointer moves, captured graphs
+        stay valid.  Training calls, capture(), set_ema() and a nested ema_weights() raise VitpeError inside."""
+        self._ema_guard("ema_weights")
+        self._ema_needs_on("ema_weights")
+        self._ema_swap()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._ema_swap()
+            self._ema_swapped = False
+
+    def _param_spans(self):
+        """(state_dict key, offset into the flat buffers, parameter) of every parameter."""
+        return [(name, self._off[id(prm)], prm) for name, prm in self.model.named_parameters(remove_duplicate=False)]
+
+    def ema_state_dict(self):
+        """model.state_dict() with every parameter entry replaced by a clone of its average (buffers as they are); nothing
+        is swapped.  Inside ema_weights() the same values (they sit in flat_p then)."""
+        self._ema_needs_on("ema_state_dict")
+        src = self.flat_p if self._ema_swapped else self.flat_e
+        sd = self.model.state_dict()
+        for name, o, prm in self._param_spans():
+            sd[name] = src[o:o + prm.numel()].view(prm.shape).clone()
+        return sd
+
+    def load_ema_state_dict(self, sd):
+        """The inverse of ema_state_dict(): the parameter entries of `sd` become the average (other keys are ignored; a
+        missing or mis-shaped parameter raises VitpeError).  The parameters themselves are not touched."""
+        self._ema_guard("load_ema_state_dict")
+        self._ema_needs_on("load_ema_state_dict")
+        spans = self._param_spans()
+        for name, _, prm in spans:
+            if name not in sd or tuple(sd[name].shape) != tuple(prm.shape):
+                raise L.VitpeError(f"load_ema_state_dict: no entry of shape {tuple(prm.shape)} for parameter {name!r}")
+        for name, o, prm in spans:
+            self.flat_e[o:o + prm.numel()].view(prm.shape).copy_(sd[name])
 
     def grad_norm(self) -> float:
         """total_norm of the last optimizer step, before clipping (what clip_grad_norm_ returns), read from hp[10];
@@ -739,6 +847,8 @@ class TrainEngine:
         K.adamw_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.hp, shadow_bf16=self.flat_s, ticked=self._ticked,
                      zero_grad=True, clipped=clip)
         self._ticked = False
+        if self.ema_decay is not None:   # on the updated parameters; hp[5] already counts this step
+            K.ema_update(self.flat_p, self.flat_e, self.hp, self.ema_warmup)
         self.refresh_shadows(cast_flat=False)
         if self.extras:   # the step's last launch, after the backward has regenerated the forward's masks: the next step
             K.rng_advance(self.rng_table, 1)   # (or replay) draws new ones.  Once per step in every step shape
@@ -775,11 +885,15 @@ class TrainEngine:
         if self.world > 1:
             ddp.broadcast_(self.flat_p, src, self.pg)
             self.refresh_shadows()
+        if self.ema_decay is not None:   # the average of parameters that have just been replaced means nothing
+            self.reset_ema()
 
     def capture(self):
         """Warm up on a side stream, then capture forward+loss+backward (and, single-GPU, the
         optimizer) into HIP graphs.  Engine state is restored after the warm-up."""
+        self._ema_guard("capture")
         state = (self.flat_p, self.flat_m, self.flat_v, self.hp, self.metric_acc) + ((self.rng_table,) if self.extras else ())
+        state += (self.flat_e,) if self.ema_decay is not None else ()   # (the warm-up's two steps would move the average)
         state += (self.aug_rng,) if self.aug_rng is not None else ()
         snap = [t.clone() for t in state]
         s = torch.cuda.Stream()
@@ -878,6 +992,7 @@ class TrainEngine:
         batch (n < B; the reference DataLoader has no drop_last, train.py:89-90) runs through the same captured
         graph with the padding masked on the device.  `n_valid_global`: size of the global batch over all ranks
         (default n * world); `n_valid` < n marks trailing indices as padding too (a rank with an empty share)."""
+        self._ema_guard("step_indexed")
         n = self._load_indices(idx)
         self.set_valid(n if n_valid is None else min(n, n_valid), n_valid_global)
         self.step()
@@ -920,6 +1035,7 @@ class TrainEngine:
         n <= B (a ragged last batch is padded and masked, see set_valid); None re-uses the resident batch.  No host
         synchronisation.  `exchange=False` skips the gradient all-reduce (measurement of the exposed communication
         time only: the replicas diverge)."""
+        self._ema_guard("step")
         if self.aug_rng is not None and self.dataset is None:   # never train silently without the crop
             raise L.VitpeError(self._AUG_NEEDS_DATASET)
         if images is not None:
@@ -965,6 +1081,7 @@ class TrainEngine:
 
     def forward_backward(self):
         """forward + loss + backward on the resident batch without the optimizer (tests / parity)."""
+        self._ema_guard("forward_backward")
         self._fwd_train(); self._loss(tick=False); self._backward()
 
     def forward_only(self, images: torch.Tensor, labels: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -1039,6 +1039,31 @@ def grad_clip(g, hp, partial):
     check(lib().vitpe_grad_clip(ptr(g), g.numel(), ptr(hp), ptr(partial), partial.numel(), stream_ptr()), "vitpe_grad_clip")
 
 
+def ema_blocks(n: int) -> int:
+    """Workgroups ema_update / ema_swap launch for n elements (the grid cap shows at n >= 2048 * 256 * 4)."""
+    return lib().vitpe_ema_blocks(int(n))
+
+
+def ema_update(p, e, hp, warmup=False):
+    """e += (1 - d_t) * (p - e) on the flat fp32 buffers, one launch: d_t = hp[13], or with warmup
+    min(hp[13], (1 + t) / (10 + t)) at t = hp[5] - hp[14]; d_t is left in hp[15] (include/vitpe.h).  p is only read."""
+    require_device(p, e, hp)
+    _f32(p, "p"); _f32(e, "e"); _f32(hp, "hp")
+    if hp is None or hp.numel() < 16 or e.numel() != p.numel():
+        raise L.VitpeError("ema_update: hp must hold 16 floats and e as many elements as p")
+    check(lib().vitpe_ema_update(ptr(p), ptr(e), ptr(hp), p.numel(), int(bool(warmup)), stream_ptr()), "vitpe_ema_update")
+
+
+def ema_swap(p, e, shadow_bf16=None):
+    """p <-> e in place; shadow_bf16 (optional) = bf16 of the new p, as cast() rounds.  Twice restores every bit."""
+    require_device(p, e, shadow_bf16)
+    _f32(p, "p"); _f32(e, "e")
+    if e.numel() != p.numel() or (shadow_bf16 is not None and (shadow_bf16.dtype != torch.bfloat16 or
+                                                               shadow_bf16.numel() != p.numel())):
+        raise L.VitpeError("ema_swap: e (fp32) and shadow_bf16 (bf16) must hold as many elements as p")
+    check(lib().vitpe_ema_swap(ptr(p), ptr(e), ptr(shadow_bf16), p.numel(), stream_ptr()), "vitpe_ema_swap")
+
+
 def cast(src, dtype, out=None):
     require_device(src, out)
     _f32(src, "src")
