@@ -297,26 +297,33 @@ def patch_embed(cfg: VitConfig, params, images):
     return x
 
 
-def forward_features(cfg: VitConfig, params, images):
-    """vit.py:235-271."""
+def _ln_eps(ln_eps, module: str) -> float:
+    """eps of the LayerNorm `module` ("blocks.0.norm1", ..., "norm"): nn.LayerNorm's 1e-5 unless `ln_eps` names another."""
+    return 1e-5 if ln_eps is None else float(ln_eps.get(module, 1e-5))
+
+
+def forward_features(cfg: VitConfig, params, images, ln_eps=None):
+    """vit.py:235-271.  ln_eps (optional): {LayerNorm module name: eps}, 1e-5 for every module it leaves out."""
     x = patch_embed(cfg, params, images)
     freqs_cis, bias = pe_tables(cfg, params)
     d = cfg.embed_dim
     for i in range(cfg.depth):
         pre = f"blocks.{i}."
-        xn = F.layer_norm(x, (d,), params[pre + "norm1.weight"], params[pre + "norm1.bias"], 1e-5)
+        xn = F.layer_norm(x, (d,), params[pre + "norm1.weight"], params[pre + "norm1.bias"],
+                          _ln_eps(ln_eps, pre + "norm1"))
         a = fused_attention(xn, params[pre + "attn.qkv.weight"], cfg.num_heads, freqs_cis, bias)
         x = x + F.linear(a, params[pre + "attn.proj.weight"], params[pre + "attn.proj.bias"])
-        xn = F.layer_norm(x, (d,), params[pre + "norm2.weight"], params[pre + "norm2.bias"], 1e-5)
+        xn = F.layer_norm(x, (d,), params[pre + "norm2.weight"], params[pre + "norm2.bias"],
+                          _ln_eps(ln_eps, pre + "norm2"))
         x = x + mlp(xn, params[pre + "mlp.fc1.weight"], params[pre + "mlp.fc1.bias"],
                     params[pre + "mlp.fc2.weight"], params[pre + "mlp.fc2.bias"])
     return x
 
 
-def forward(cfg: VitConfig, params, images):
+def forward(cfg: VitConfig, params, images, ln_eps=None):
     """logits [B,num_classes]; vit.py:283-285."""
-    x = forward_features(cfg, params, images)
-    x = F.layer_norm(x, (cfg.embed_dim,), params["norm.weight"], params["norm.bias"], 1e-5)
+    x = forward_features(cfg, params, images, ln_eps)
+    x = F.layer_norm(x, (cfg.embed_dim,), params["norm.weight"], params["norm.bias"], _ln_eps(ln_eps, "norm"))
     return F.linear(x[:, 0], params["head.weight"], params["head.bias"])
 
 
@@ -480,11 +487,11 @@ def adamw_update(params, grads, st: AdamWState, lr=1e-3, betas=(0.9, 0.999), eps
         p.addcdiv_(st.m[k], denom, value=-lr / bc1)
 
 
-def loss_and_grads(cfg: VitConfig, params, images, labels):
-    """forward -> mean CE -> backward via autograd on the restatement."""
+def loss_and_grads(cfg: VitConfig, params, images, labels, ln_eps=None):
+    """forward -> mean CE -> backward via autograd on the restatement (ln_eps: as forward_features)."""
     leaves = {k: v.detach().clone().requires_grad_(v.is_floating_point() and k != "pos_embed.inv_freq")
               for k, v in params.items()}
-    logits = forward(cfg, leaves, images)
+    logits = forward(cfg, leaves, images, ln_eps)
     loss = loss_fn(logits, labels)
     names = [k for k, v in leaves.items() if v.requires_grad]
     gs = torch.autograd.grad(loss, [leaves[k] for k in names], allow_unused=True)

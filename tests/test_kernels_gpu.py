@@ -640,6 +640,7 @@ def test_layernorm_fwd_bwd(K, dt, M, D):
     y, mean, rstd = K.layernorm_fwd(dev(x, DT[dt]), dev(g), dev(b))
     assert rel_err(y.float().cpu(), yr.detach()) < tol(dt)
     assert rel_err(mean.cpu(), x.to(DT[dt]).float().mean(-1)) < 1e-5
+    assert rel_err(rstd.cpu(), (q(x, dt).double().var(-1, unbiased=False) + 1e-5).rsqrt()) < 1e-5
     dgam = torch.zeros(D, device="cuda")
     dbet = torch.zeros(D, device="cuda")
     dx = K.layernorm_bwd(dev(dy, DT[dt]), dev(x, DT[dt]), mean, rstd, dev(g), dgam, dbet, dres=dev(dres, DT[dt]))
