@@ -510,6 +510,33 @@ int vitpe_head_step(int dtype, const void* x, const float* gamma, const float* b
  * bit 2 = the gradient is scaled by hp[9] instead of hp[8] (after vitpe_grad_clip).  Values 0..3 never read hp[9].  */
 int vitpe_adamw_step(float* p, float* g, float* m, float* v, void* shadow_bf16, float* hp,
                      long long n, int zero_grad, vitpe_stream_t stream);
+/* AdamW with parameter groups (replaces the one group of train.py:195-196): vitpe_adamw_step's arithmetic, hp slots and
+ * zero_grad bits, with a (learning-rate, weight-decay) SCALE pair per group.  The 8-element granule i / 8 of the flat
+ * buffers belongs to group k = gid[i / 8] (one byte per granule; n_gid >= ceil(n / 8) bytes; ids >= n_groups are read as
+ * n_groups - 1), and group k uses lr_k = hp[0] * gtab[2k], wd_k = hp[4] * gtab[2k+1] (gtab: n_groups fp32 pairs): decay
+ * factor 1 - lr_k * wd_k, step size lr_k / bc1.  With every scale 1.0 the result is vitpe_adamw_step's bit for bit (p, m,
+ * v, g, shadow).  One lane per granule (16-byte loads and stores, 8-byte shadow stores), the n % 8 last elements one lane
+ * each; grid-stride over vitpe_adamw_groups_blocks(n) workgroups of 256: the grid depends on n alone.  n == 0 launches only
+ * the tick (unless bit 1 is set).  hipErrorInvalidValue, and nothing launched, for NULL hp; NULL p / g / m / v / gid / gtab
+ * with n > 0; n < 0; n_groups outside 1..256; n_gid < ceil(n / 8); p, g, m or v not 16-byte aligned; a shadow not 8-byte
+ * aligned.                                                                                                           */
+int vitpe_adamw_step_groups(float* p, float* g, float* m, float* v, void* shadow_bf16, float* hp, long long n,
+                            int zero_grad, const unsigned char* gid, long long n_gid, const float* gtab, int n_groups,
+                            vitpe_stream_t stream);
+/* workgroups vitpe_adamw_step_groups launches for n elements: min(2048, max(1, ceil(ceil(n / 8) / 256))); 0 for n <= 0 */
+int vitpe_adamw_groups_blocks(long long n);
+/* Linear warm-up + cosine learning rate, stepped once per iteration on the device (replaces the per-epoch
+ * CosineAnnealingLR of train.py:205; equals SequentialLR(LinearLR(start_factor=s0, total_iters=W),
+ * CosineAnnealingLR(T_max=T-W, eta_min=min_lr), milestones=[W]) for k <= T).  sched (device, 8 floats): [0]=base_lr
+ * [1]=min_lr [2]=W warm-up steps [3]=T total steps [4]=s0 start factor [5]=origin (hp[5] when the schedule was switched
+ * on, less the steps already done) [6]=the last lr written [7]=unused.  One lane, fp64:
+ *   k = max(0, hp[5] - sched[5] - (ticked ? 1 : 0))      (ticked: vitpe_head_step already advanced hp[5] for this step)
+ *   k < W : lr = base * (s0 + (1 - s0) * k / W)
+ *   k >= T: lr = min_lr
+ *   else  : c = cos(pi / 2 * (k - W) / (T - W)),  lr = min_lr + (base - min_lr) * c * c
+ * hp[0] = sched[6] = (float)lr; nothing else is written.  Call it before vitpe_grad_clip / the AdamW call of the step.
+ * T > W >= 0, 0 < s0 <= 1, 0 <= min_lr <= base are the writer's duty.  hipErrorInvalidValue for NULL pointers.       */
+int vitpe_lr_schedule(float* hp, const float* sched, int ticked, vitpe_stream_t stream);
 /* torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2.0, error_if_nonfinite=False) on the flat gradient g [n]
  * (4-byte aligned; any offset inside a 16-byte line), as two launches without atomics and without a host read:
  *   hp[10] = total_norm = hp[8] * sqrt(sum g[i]^2)      (the norm of the gradient AdamW uses, g * grad_scale)

@@ -15,7 +15,10 @@ device: torchvision and the dataset downloads are unavailable offline), --steps_
 RandomHorizontalFlip on the training images, drawn inside the embed kernel), --clip_grad MAX_NORM
 (torch.nn.utils.clip_grad_norm_ between backward and the optimizer step, inside the captured step), --model_ema DECAY /
 --model_ema_warmup (an exponential moving average of the weights, updated inside the captured step; every epoch also
-evaluates the average and keeps its best checkpoint).  --batch_size is the GLOBAL batch.
+evaluates the average and keeps its best checkpoint), --no_decay_norm_bias / --layer_decay D (AdamW parameter groups:
+no weight decay on 1-d and position parameters, layer-wise learning-rate decay), --warmup_epochs E / --min_lr /
+--lr_per_step (linear warm-up + cosine learning rate stepped every iteration, inside the captured step).  --batch_size is
+the GLOBAL batch.
 """
 import argparse
 import csv
@@ -79,7 +82,25 @@ def get_args(argv=None):
                              'and save its best checkpoint (0 = off)')
     parser.add_argument('--model_ema_warmup', action='store_true',
                         help='ramp the decay up as min(DECAY, (1 + t) / (10 + t)) over the optimizer steps t')
+    # AdamW parameter groups and the per-step schedule (TrainEngine.set_param_groups / set_lr_schedule); all off by default
+    parser.add_argument('--no_decay_norm_bias', action='store_true',
+                        help='no weight decay on 1-d parameters (norms, biases), the class token and the position parameters')
+    parser.add_argument('--layer_decay', type=float, default=0.0, metavar='D',
+                        help='layer-wise learning-rate decay: a layer k levels below the head trains at lr * D^k (0 = off)')
+    parser.add_argument('--warmup_epochs', type=float, default=0.0, metavar='E',
+                        help='linear warm-up over the first E epochs (a fraction is fine), then a per-step cosine')
+    parser.add_argument('--min_lr', type=float, default=0.0, help='where the per-step cosine ends')
+    parser.add_argument('--lr_per_step', action='store_true',
+                        help='step the cosine every iteration on the device instead of once per epoch from the host')
     args = parser.parse_args(argv)
+    if not (math.isfinite(args.layer_decay) and 0.0 <= args.layer_decay <= 1.0):
+        parser.error("--layer_decay must be 0 (off) or a factor in (0, 1]")
+    if not (math.isfinite(args.warmup_epochs) and 0.0 <= args.warmup_epochs < args.epochs):
+        parser.error("--warmup_epochs must be a finite number in [0, --epochs)")
+    if not (math.isfinite(args.min_lr) and 0.0 <= args.min_lr <= args.lr):
+        parser.error("--min_lr must be in [0, --lr]")
+    if args.min_lr > 0.0 and not (args.warmup_epochs > 0.0 or args.lr_per_step):
+        parser.error("--min_lr belongs to the per-step schedule: it needs --warmup_epochs E or --lr_per_step")
     if not (math.isfinite(args.model_ema) and 0.0 <= args.model_ema < 1.0):
         parser.error("--model_ema must be 0 (off) or a decay in (0, 1)")
     if args.model_ema_warmup and args.model_ema == 0.0:
@@ -308,12 +329,21 @@ def main(argv=None):
     use_ema = args.model_ema > 0
     if use_ema:   # after the broadcast: the average starts from the parameters every rank trains
         engine.set_ema(args.model_ema, warmup=args.model_ema_warmup)
+    if args.no_decay_norm_bias or args.layer_decay > 0:   # every rank builds the same map
+        from vitpe.engine import vit_param_groups
+        engine.set_param_groups(vit_param_groups(model, no_decay=args.no_decay_norm_bias, layer_decay=args.layer_decay or None))
+    per_step = args.warmup_epochs > 0 or args.lr_per_step
+    if per_step:   # linear warm-up + cosine, stepped by the captured step itself: one schedule over the whole run
+        steps_per_epoch = len(train_loader)
+        warm = min(round(args.warmup_epochs * steps_per_epoch), args.epochs * steps_per_epoch - 1)
+        engine.set_lr_schedule(args.lr, args.epochs * steps_per_epoch, warm, args.min_lr)
 
     best_acc = 0
     best_ema_acc = -1.0   # (the first epoch's average is always a checkpoint, also at 0 % on a toy run)
     for epoch in range(args.epochs):
         # CosineAnnealingLR(T_max=epochs), stepped per epoch (reference train.py:196,205)
-        engine.set_lr(0.5 * args.lr * (1 + math.cos(math.pi * epoch / args.epochs)))
+        if not per_step:
+            engine.set_lr(0.5 * args.lr * (1 + math.cos(math.pi * epoch / args.epochs)))
         train_loss, train_acc = train(engine, train_loader)
         test_loss, test_acc = test(engine, test_loader)
         ema_cols = []

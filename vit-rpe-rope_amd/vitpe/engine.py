@@ -77,6 +77,58 @@ def engine_unsupported(model):
     return sorted(set(active))
 
 
+def vit_layer_id(name: str, depth: int) -> int:
+    """Layer index of parameter `name` for layer-wise learning-rate decay (timm's rule): 0 for the patch embedding, the
+    class token and the position parameters, i + 1 for blocks.i.*, depth + 1 for the final norm and the head."""
+    if name.startswith("blocks."):
+        return int(name.split(".")[1]) + 1
+    if name == "cls_token" or name.startswith(("patch_embed.", "pos_embed.")):
+        return 0
+    return depth + 1
+
+
+def vit_param_groups(model, no_decay: bool = True, layer_decay: Optional[float] = None):
+    """The AdamW parameter groups ViT recipes use, as TrainEngine.set_param_groups takes them (pure host code: works on a
+    CPU model).  no_decay: weight_decay_scale 0 for parameters with ndim <= 1 (LayerNorm gains, biases), cls_token and
+    everything under pos_embed. (the absolute table, the relative bias table, the polynomial coefficients, the
+    rope-mixed freqs).  layer_decay = d: lr_scale = d ** (depth + 1 - vit_layer_id(name)).  Every parameter is in exactly
+    one group; a group also carries its "names" and, with layer_decay, its "layer_id" (set_param_groups ignores both)."""
+    if layer_decay is not None and not (math.isfinite(float(layer_decay)) and float(layer_decay) > 0.0):
+        raise L.VitpeError(f"vit_param_groups: layer_decay must be None or a finite number > 0, got {layer_decay!r}")
+    depth = len(model.blocks)
+    groups: Dict[tuple, dict] = {}
+    for name, prm in model.named_parameters():
+        skip = no_decay and (prm.ndim <= 1 or name == "cls_token" or name.startswith("pos_embed."))
+        lid = vit_layer_id(name, depth) if layer_decay is not None else None
+        key = (lid, skip)
+        if key not in groups:
+            groups[key] = {"params": [], "names": [], "layer_id": lid,
+                           "lr_scale": 1.0 if lid is None else float(layer_decay) ** (depth + 1 - lid),
+                           "weight_decay_scale": 0.0 if skip else 1.0}
+        groups[key]["params"].append(prm)
+        groups[key]["names"].append(name)
+    return list(groups.values())
+
+
+def torch_param_groups(groups, lr: float, weight_decay: float):
+    """`groups` (vit_param_groups / set_param_groups format) as torch.optim.AdamW's param groups: the module path's
+    equivalent of set_param_groups on an engine built with the same lr and weight_decay."""
+    return [{"params": list(g["params"]), "lr": lr * float(g.get("lr_scale", 1.0)),
+             "weight_decay": weight_decay * float(g.get("weight_decay_scale", 1.0))} for g in groups]
+
+
+def param_granule_map(spans, n_flat: int):
+    """uint8 [n_flat / ALIGN]: the group of every ALIGN-element granule of the flat buffers.  spans: (offset, numel, group)
+    per parameter (offsets are multiples of ALIGN, so no granule spans two parameters: a parameter's last granule is its
+    group's together with the zero padding in it, which every group leaves zero); a granule no parameter covers is group 0."""
+    assert n_flat % ALIGN == 0
+    gid = np.zeros(n_flat // ALIGN, dtype=np.uint8)
+    for off, numel, k in spans:
+        assert off % ALIGN == 0 and 0 <= k < 256
+        gid[off // ALIGN:(off + numel + ALIGN - 1) // ALIGN] = k
+    return gid
+
+
 class TrainEngine:
     # defaults of the two attributes set_grad_clip() / grad_norm() read, so that they answer on an object that never ran
     # __init__ (tests/test_grad_clip_cpu.py checks their argument handling without a device); __init__ sets both
@@ -85,6 +137,10 @@ class TrainEngine:
     # switch, and whether ema_weights() currently has the average swapped into flat_p
     ema_decay = flat_e = None
     ema_warmup = _ema_swapped = False
+    # and set_param_groups() / set_lr_schedule() / set_lr() (tests/test_optim_groups_cpu.py): the normalised group list
+    # (None = one group, vitpe_adamw_step), its device map and scale table; the schedule's host copy (None = off) and block
+    param_groups = _gid = _gid_host = _gtab = None
+    lr_sched = _sched = None
 
     def __init__(self, model: VisionTransformer, batch_size: int, compute_dtype=torch.bfloat16, lr=1e-3,
                  weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, process_group=None, use_graph=True, fuse_ln=None,
@@ -123,6 +179,8 @@ class TrainEngine:
         self.clip_max_norm = self._clip_partial = None     # set_grad_clip(): None = clipping off; the clip's work buffer
         self.ema_decay = self.flat_e = None                # set_ema(): None = no average kept
         self.ema_warmup = self._ema_swapped = False
+        self.param_groups = self._gid = self._gid_host = self._gtab = None   # set_param_groups(): None = one group
+        self.lr_sched = self._sched = None                 # set_lr_schedule(): None = hp[0] moves only by set_lr()
         self._build_flat(lr, weight_decay, betas, eps)
         self._build_buffers()
         self._build_rng_table()
@@ -277,7 +335,123 @@ class TrainEngine:
         K.refresh_shadows(self.flat_p, self._shadow_flat, self._desc, self._ndesc, self._ntiles, self._tile_map)
 
     def set_lr(self, lr: float):
+        if self.lr_sched is not None:
+            raise L.VitpeError("set_lr: a per-step schedule is on and writes hp[0] every step (set_lr_schedule(None) first, "
+                               "or give the schedule its new base_lr)")
         self.hp[0] = lr
+
+    def current_lr(self) -> float:
+        """hp[0], the learning rate of the last step (the base rate every group scales); synchronises with the device."""
+        return float(self.hp[0].item())
+
+    # ---------------------------------------------------------------- AdamW parameter groups / LR schedule
+    @staticmethod
+    def _group_scales(groups):
+        """set_param_groups' argument, checked as far as host logic goes: [(params, lr_scale, weight_decay_scale)], or None
+        for None / [].  VitpeError for a malformed group, a scale that is not finite and >= 0, a parameter listed twice or
+        more than 255 groups (the map is one byte per granule; group 0 is the unlisted parameters')."""
+        if groups is None or len(groups) == 0:
+            return None
+        out, seen = [], set()
+        for grp in groups:
+            if not isinstance(grp, dict) or "params" not in grp:
+                raise L.VitpeError("set_param_groups: every group is a dict with a 'params' list")
+            scales = []
+            for key in ("lr_scale", "weight_decay_scale"):
+                try:
+                    value = float(grp.get(key, 1.0))
+                except (TypeError, ValueError):
+                    value = float("nan")
+                if not math.isfinite(value) or value < 0.0:
+                    raise L.VitpeError(f"set_param_groups: {key} must be a finite number >= 0, got {grp.get(key)!r}")
+                scales.append(value)
+            params = list(grp["params"])
+            for prm in params:
+                if id(prm) in seen:
+                    raise L.VitpeError("set_param_groups: a parameter is listed twice")
+                seen.add(id(prm))
+            out.append((params, scales[0], scales[1]))
+        if len(out) > 255:
+            raise L.VitpeError(f"set_param_groups: at most 255 groups, got {len(out)}")
+        return out
+
+    def set_param_groups(self, groups):
+        """AdamW parameter groups inside the step ("Parameter groups and LR schedule"): `groups` is a list of
+        {"params": [...], "lr_scale": float, "weight_decay_scale": float} (both scales default to 1, finite and >= 0); the
+        parameters of a group train at lr * lr_scale with weight decay weight_decay * weight_decay_scale, parameters not
+        listed at (1, 1).  vit_param_groups(model, ...) builds the usual list.  None or [] switches the groups off (the
+        default: vitpe_adamw_step, one group).  Scales, not values: set_lr, set_lr_schedule and the engine's weight_decay
+        keep working.  Configuration like max_norm: not part of state_dict().  Switching on or off, or another partition of
+        the parameters, drops the captured graphs; the same partition with new scales is one device write and keeps them.
+        A parameter listed twice or not the model's raises VitpeError.  Every rank must make the same call."""
+        new = self._group_scales(groups)
+        if new is None:
+            if self.param_groups is not None:
+                self._drop_graphs()
+            self.param_groups = self._gid = self._gid_host = self._gtab = None
+            return
+        spans, table = [], [(1.0, 1.0)]
+        for k, (params, lr_scale, wd_scale) in enumerate(new, start=1):
+            table.append((lr_scale, wd_scale))
+            for prm in params:
+                if id(prm) not in self._off:
+                    raise L.VitpeError("set_param_groups: a listed parameter is not one of the model's")
+                spans.append((self._off[id(prm)], prm.numel(), k))
+        gid = param_granule_map(spans, self.n_flat)
+        gtab = torch.tensor(table, dtype=torch.float32)
+        if self._gid_host is not None and self._gtab.shape == gtab.shape and np.array_equal(gid, self._gid_host):
+            self._gtab.copy_(gtab)   # the captured launches read the same two buffers
+        else:
+            self._gid_host, self._gid, self._gtab = gid, torch.from_numpy(gid).to(self.dev), gtab.to(self.dev)
+            self._drop_graphs()
+        self.param_groups = new
+
+    @staticmethod
+    def _sched_values(base_lr, total_steps, warmup_steps, min_lr, warmup_factor, done):
+        """set_lr_schedule's arguments as (base, min, W, T, s0, done), or None for base_lr None; VitpeError unless
+        T > W >= 0, 0 < s0 <= 1, 0 <= min_lr <= base_lr, done >= 0, all finite (T and done below 2^24: fp32 counters)."""
+        if base_lr is None:
+            return None
+        try:
+            base, lo, s0 = float(base_lr), float(min_lr), float(warmup_factor)
+            T, W, dn = int(total_steps), int(warmup_steps), int(done)
+            whole = (T == total_steps and W == warmup_steps and dn == done)
+        except (TypeError, ValueError, OverflowError):
+            base, whole = float("nan"), False
+        if not (whole and all(math.isfinite(x) for x in (base, lo, s0)) and 0.0 <= lo <= base and 0.0 < s0 <= 1.0
+                and 0 <= W < T < 2 ** 24 and 0 <= dn < 2 ** 24):
+            raise L.VitpeError(f"set_lr_schedule: needs total_steps > warmup_steps >= 0, 0 < warmup_factor <= 1, "
+                               f"0 <= min_lr <= base_lr and done >= 0, got base_lr={base_lr!r} total_steps={total_steps!r} "
+                               f"warmup_steps={warmup_steps!r} min_lr={min_lr!r} warmup_factor={warmup_factor!r} done={done!r}")
+        return base, lo, W, T, s0, dn
+
+    def set_lr_schedule(self, base_lr: Optional[float], total_steps: int = 0, warmup_steps: int = 0, min_lr: float = 0.0,
+                        warmup_factor: float = 1e-3, done: int = 0):
+        """Linear warm-up + cosine learning rate, stepped every iteration inside the step ("Parameter groups and
+        LR schedule"): step k = `done`, done + 1, ... of the schedule trains at
+            base_lr * (warmup_factor + (1 - warmup_factor) * k / warmup_steps)                      k < warmup_steps
+            min_lr + (base_lr - min_lr) * cos^2(pi / 2 * (k - warmup_steps) / (total_steps - warmup_steps))   up to total_steps
+        and at min_lr from then on -- torch's SequentialLR(LinearLR, CosineAnnealingLR) stepped once per iteration.  The
+        step counter is the optimizer's own, on the device, so replays of the captured step follow the schedule without a
+        host write.  None as base_lr switches the schedule off (the default; hp[0] keeps its last value).  Switching on or
+        off drops the captured graphs; new values for an enabled schedule (the call re-bases it: the next step is step
+        `done`) are device writes and keep them.  Configuration like max_norm: not part of state_dict() -- `done=` is how a
+        resumed run continues.  While it is on, set_lr() raises VitpeError."""
+        new = self._sched_values(base_lr, total_steps, warmup_steps, min_lr, warmup_factor, done)
+        if new is None:
+            if self.lr_sched is not None:
+                self._drop_graphs()
+            self.lr_sched = self._sched = None
+            return
+        base, lo, W, T, s0, dn = new
+        if self._sched is None:
+            self._sched = torch.zeros(8, dtype=torch.float32, device=self.dev)
+            self._drop_graphs()
+        self._sched[:5] = torch.tensor([base, lo, float(W), float(T), s0], dtype=torch.float32, device=self.dev)
+        self._sched[5:6].copy_(self.hp[5:6])   # origin = hp[5] - done, device to device (no host read of the counter)
+        if dn:
+            self._sched[5:6].sub_(float(dn))
+        self.lr_sched = new
 
     def set_grad_clip(self, max_norm: Optional[float]):
         """torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) between the backward (after every all-reduce) and
@@ -842,10 +1016,16 @@ class TrainEngine:
 
     def _optimizer(self):
         clip = self.clip_max_norm is not None
+        if self.lr_sched is not None:   # hp[0] of this step, before anything reads it
+            K.lr_schedule(self.hp, self._sched, ticked=self._ticked)
         if clip:   # after every all-reduce in every step shape: all ranks reduce the same flat_g to the same coefficient
             K.grad_clip(self.flat_g, self.hp, self._clip_partial)
-        K.adamw_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.hp, shadow_bf16=self.flat_s, ticked=self._ticked,
-                     zero_grad=True, clipped=clip)
+        if self.param_groups is None:
+            K.adamw_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.hp, shadow_bf16=self.flat_s,
+                         ticked=self._ticked, zero_grad=True, clipped=clip)
+        else:
+            K.adamw_step_groups(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.hp, self._gid, self._gtab,
+                                shadow_bf16=self.flat_s, ticked=self._ticked, zero_grad=True, clipped=clip)
         self._ticked = False
         if self.ema_decay is not None:   # on the updated parameters; hp[5] already counts this step
             K.ema_update(self.flat_p, self.flat_e, self.hp, self.ema_warmup)
@@ -895,6 +1075,7 @@ class TrainEngine:
         state = (self.flat_p, self.flat_m, self.flat_v, self.hp, self.metric_acc) + ((self.rng_table,) if self.extras else ())
         state += (self.flat_e,) if self.ema_decay is not None else ()   # (the warm-up's two steps would move the average)
         state += (self.aug_rng,) if self.aug_rng is not None else ()
+        state += (self._sched,) if self.lr_sched is not None else ()    # (sched[6]; hp[0] and hp[5] return with hp)
         snap = [t.clone() for t in state]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())

@@ -1023,6 +1023,49 @@ def adamw_step(p, g, m, v, hp, shadow_bf16=None, zero_grad=True, ticked=False, c
                                  stream_ptr()), "vitpe_adamw_step")
 
 
+def adamw_groups_blocks(n: int) -> int:
+    """Workgroups adamw_step_groups launches for n elements (the grid cap shows at n >= 2048 * 256 * 8)."""
+    return lib().vitpe_adamw_groups_blocks(int(n))
+
+
+def adamw_step_groups(p, g, m, v, hp, gid, gtab, shadow_bf16=None, zero_grad=True, ticked=False, clipped=False):
+    """adamw_step with parameter groups: granule i / 8 of the flat buffers belongs to group gid[i / 8] (uint8, one byte per
+    8 elements), which trains at lr = hp[0] * gtab[k, 0] and weight decay hp[4] * gtab[k, 1] (gtab: fp32 [n_groups, 2]);
+    everything else as adamw_step, whose result it equals bit for bit when every scale is 1 (include/vitpe.h)."""
+    require_device(p, g, m, v, hp, gid, gtab, shadow_bf16)
+    for t, name in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (hp, "hp"), (gtab, "gtab")):
+        if t is None:
+            raise L.VitpeError(f"adamw_step_groups: {name} is missing")
+        _f32(t, name)
+    n = p.numel()
+    if gid is None or gid.dtype != torch.uint8:
+        raise L.VitpeError("adamw_step_groups: gid must be a uint8 tensor, one byte per 8-element granule")
+    if hp.numel() < 16 or g.numel() != n or m.numel() != n or v.numel() != n:
+        raise L.VitpeError("adamw_step_groups: hp must hold 16 floats and g, m, v as many elements as p")
+    if gtab.numel() < 2 or gtab.numel() % 2 or gtab.numel() > 512:
+        raise L.VitpeError(f"adamw_step_groups: gtab must hold 1..256 (lr, weight decay) scale pairs, got {gtab.numel()} floats")
+    if gid.numel() < (n + 7) // 8:
+        raise L.VitpeError(f"adamw_step_groups: gid holds {gid.numel()} granules, {n} elements need {(n + 7) // 8}")
+    if shadow_bf16 is not None and (shadow_bf16.dtype != torch.bfloat16 or shadow_bf16.numel() != n):
+        raise L.VitpeError("adamw_step_groups: shadow_bf16 (bf16) must hold as many elements as p")
+    check(lib().vitpe_adamw_step_groups(ptr(p), ptr(g), ptr(m), ptr(v), ptr(shadow_bf16), ptr(hp), n,
+                                        int(bool(zero_grad)) | (2 if ticked else 0) | (4 if clipped else 0),
+                                        ptr(gid), gid.numel(), ptr(gtab), gtab.numel() // 2, stream_ptr()),
+          "vitpe_adamw_step_groups")
+
+
+def lr_schedule(hp, sched, ticked=False):
+    """hp[0] = sched[6] = the linear warm-up + cosine learning rate of step k = hp[5] - sched[5] (- 1 when `ticked`: the
+    head already advanced the counter), one lane on the device; sched: the 8-float block of include/vitpe.h."""
+    require_device(hp, sched)
+    if hp is None or sched is None:
+        raise L.VitpeError("lr_schedule: hp and sched are required")
+    _f32(hp, "hp"); _f32(sched, "sched")
+    if hp.numel() < 16 or sched.numel() < 8:
+        raise L.VitpeError("lr_schedule: hp must hold 16 floats and sched 8")
+    check(lib().vitpe_lr_schedule(ptr(hp), ptr(sched), int(bool(ticked)), stream_ptr()), "vitpe_lr_schedule")
+
+
 def grad_clip_blocks(n: int) -> int:
     """Floats of the work buffer grad_clip needs for a gradient of n elements."""
     return lib().vitpe_grad_clip_blocks(int(n))
