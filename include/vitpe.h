@@ -491,7 +491,7 @@ int vitpe_head_bwd(int dtype, const float* dlogits, const float* Wh, const float
  * D <= 768, else hipErrorNotSupported).  ctl as vitpe_cross_entropy_ctl.  dx: ONLY the class rows are written -- the
  * caller keeps rows 1.. of every image zero (they never change).  per_image: [B,2] work buffer ((loss, correct) per
  * image, summed in fixed order: no atomics on the totals).  Parameter gradients are accumulated.  hp_tick (nullable): the
- * optimizer's hp block -- the launch also advances its step counter and bias corrections ([5..7]), which lets the following
+ * optimizer's hp block -- the launch also advances hp[STEP], hp[BC1] and hp[BC2], which lets the following
  * vitpe_adamw_step skip its own one-thread launch (zero_grad bit 1).                                              */
 int vitpe_head_step(int dtype, const void* x, const float* gamma, const float* beta, const float* Wh,
                     const float* bh, const long long* labels, float* logits, float* dlogits, float* ws_xhat,
@@ -500,20 +500,48 @@ int vitpe_head_step(int dtype, const void* x, const float* gamma, const float* b
                     int D, int Cn, float eps, float* hp_tick, vitpe_stream_t stream);
 
 /* ---- optimizer + weight shadows (train.py:116,195) ------------------------------------------
- * hp (device, 16 floats): [0]=lr [1]=beta1 [2]=beta2 [3]=eps [4]=weight_decay [5]=step
- * [6]=bias_correction1 [7]=bias_correction2 [8]=grad_scale [9]=effective grad scale (grad_scale * clip_coef)
- * [10]=total_norm [11]=clip_coef [12]=max_norm ([9..11] are written by vitpe_grad_clip, [12] by the host)
- * [13]=EMA decay [14]=the step counter [5] when the EMA was switched on ([13], [14] written by the host side, read by
- * vitpe_ema_update) [15]=the decay d_t vitpe_ema_update used last.  The step counter lives on the
- * device so the call can be replayed from a hipGraph.  zero_grad: bit 0 = clear g after the update,
- * bit 1 = the step counter / bias corrections were already advanced (vitpe_head_step hp_tick),
- * bit 2 = the gradient is scaled by hp[9] instead of hp[8] (after vitpe_grad_clip).  Values 0..3 never read hp[9].  */
+ * hp (device, VITPE_HP_COUNT floats) and sched (device, VITPE_SCHED_COUNT floats) are the two blocks the calls below share;
+ * both live on the device so that the calls can be replayed from a hipGraph.  In the comments below hp[X] is short for
+ * hp[VITPE_HP_X] and sched[X] for sched[VITPE_SCHED_X].                                                              */
+enum vitpe_hp_slot {
+  VITPE_HP_LR = 0,            /* learning rate (host; vitpe_lr_schedule while a schedule is on) */
+  VITPE_HP_BETA1 = 1,         /* host */
+  VITPE_HP_BETA2 = 2,         /* host */
+  VITPE_HP_EPS = 3,           /* host */
+  VITPE_HP_WEIGHT_DECAY = 4,  /* host */
+  VITPE_HP_STEP = 5,          /* step counter (the tick: vitpe_adamw_step*, or vitpe_head_step's hp_tick) */
+  VITPE_HP_BC1 = 6,           /* bias correction 1 - beta1^step (the tick) */
+  VITPE_HP_BC2 = 7,           /* bias correction 1 - beta2^step (the tick) */
+  VITPE_HP_GRAD_SCALE = 8,    /* host: 1 / world */
+  VITPE_HP_CLIP_SCALE = 9,    /* effective gradient scale, GRAD_SCALE * CLIP_COEF (vitpe_grad_clip) */
+  VITPE_HP_TOTAL_NORM = 10,   /* vitpe_grad_clip */
+  VITPE_HP_CLIP_COEF = 11,    /* vitpe_grad_clip */
+  VITPE_HP_MAX_NORM = 12,     /* host */
+  VITPE_HP_EMA_DECAY = 13,    /* host */
+  VITPE_HP_EMA_ORIGIN = 14,   /* host side: STEP when the EMA was switched on */
+  VITPE_HP_EMA_DT = 15,       /* the decay d_t vitpe_ema_update used last */
+  VITPE_HP_COUNT = 16
+};
+enum vitpe_sched_slot {
+  VITPE_SCHED_BASE_LR = 0,
+  VITPE_SCHED_MIN_LR = 1,
+  VITPE_SCHED_WARMUP = 2,        /* W warm-up steps */
+  VITPE_SCHED_TOTAL = 3,         /* T total steps */
+  VITPE_SCHED_START_FACTOR = 4,  /* s0 */
+  VITPE_SCHED_ORIGIN = 5,        /* hp[STEP] when the schedule was switched on, less the steps already done */
+  VITPE_SCHED_LAST_LR = 6,       /* the last lr written (vitpe_lr_schedule); everything else is the host's */
+  VITPE_SCHED_SPARE = 7,
+  VITPE_SCHED_COUNT = 8
+};
+/* Fused AdamW on the flat buffers.  zero_grad: bit 0 = clear g after the update, bit 1 = the step counter / bias
+ * corrections were already advanced (vitpe_head_step hp_tick), bit 2 = the gradient is scaled by hp[CLIP_SCALE]
+ * instead of hp[GRAD_SCALE] (after vitpe_grad_clip).  Values 0..3 never read hp[CLIP_SCALE].                            */
 int vitpe_adamw_step(float* p, float* g, float* m, float* v, void* shadow_bf16, float* hp,
                      long long n, int zero_grad, vitpe_stream_t stream);
 /* AdamW with parameter groups (replaces the one group of train.py:195-196): vitpe_adamw_step's arithmetic, hp slots and
  * zero_grad bits, with a (learning-rate, weight-decay) SCALE pair per group.  The 8-element granule i / 8 of the flat
  * buffers belongs to group k = gid[i / 8] (one byte per granule; n_gid >= ceil(n / 8) bytes; ids >= n_groups are read as
- * n_groups - 1), and group k uses lr_k = hp[0] * gtab[2k], wd_k = hp[4] * gtab[2k+1] (gtab: n_groups fp32 pairs): decay
+ * n_groups - 1), and group k uses lr_k = hp[LR] * gtab[2k], wd_k = hp[WEIGHT_DECAY] * gtab[2k+1] (gtab: n_groups fp32 pairs): decay
  * factor 1 - lr_k * wd_k, step size lr_k / bc1.  With every scale 1.0 the result is vitpe_adamw_step's bit for bit (p, m,
  * v, g, shadow).  One lane per granule (16-byte loads and stores, 8-byte shadow stores), the n % 8 last elements one lane
  * each; grid-stride over vitpe_adamw_groups_blocks(n) workgroups of 256: the grid depends on n alone.  n == 0 launches only
@@ -527,22 +555,21 @@ int vitpe_adamw_step_groups(float* p, float* g, float* m, float* v, void* shadow
 int vitpe_adamw_groups_blocks(long long n);
 /* Linear warm-up + cosine learning rate, stepped once per iteration on the device (replaces the per-epoch
  * CosineAnnealingLR of train.py:205; equals SequentialLR(LinearLR(start_factor=s0, total_iters=W),
- * CosineAnnealingLR(T_max=T-W, eta_min=min_lr), milestones=[W]) for k <= T).  sched (device, 8 floats): [0]=base_lr
- * [1]=min_lr [2]=W warm-up steps [3]=T total steps [4]=s0 start factor [5]=origin (hp[5] when the schedule was switched
- * on, less the steps already done) [6]=the last lr written [7]=unused.  One lane, fp64:
- *   k = max(0, hp[5] - sched[5] - (ticked ? 1 : 0))      (ticked: vitpe_head_step already advanced hp[5] for this step)
+ * CosineAnnealingLR(T_max=T-W, eta_min=min_lr), milestones=[W]) for k <= T).  sched: enum vitpe_sched_slot (base, min_lr, W,
+ * T, s0 below).  One lane, fp64:
+ *   k = max(0, hp[STEP] - sched[ORIGIN] - (ticked ? 1 : 0))   (ticked: vitpe_head_step already advanced the counter)
  *   k < W : lr = base * (s0 + (1 - s0) * k / W)
  *   k >= T: lr = min_lr
  *   else  : c = cos(pi / 2 * (k - W) / (T - W)),  lr = min_lr + (base - min_lr) * c * c
- * hp[0] = sched[6] = (float)lr; nothing else is written.  Call it before vitpe_grad_clip / the AdamW call of the step.
+ * hp[LR] = sched[LAST_LR] = (float)lr; nothing else is written.  Call it before vitpe_grad_clip / the AdamW call of the step.
  * T > W >= 0, 0 < s0 <= 1, 0 <= min_lr <= base are the writer's duty.  hipErrorInvalidValue for NULL pointers.       */
 int vitpe_lr_schedule(float* hp, const float* sched, int ticked, vitpe_stream_t stream);
 /* torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2.0, error_if_nonfinite=False) on the flat gradient g [n]
  * (4-byte aligned; any offset inside a 16-byte line), as two launches without atomics and without a host read:
- *   hp[10] = total_norm = hp[8] * sqrt(sum g[i]^2)      (the norm of the gradient AdamW uses, g * grad_scale)
- *   hp[11] = clip_coef  = min(1, hp[12] / (total_norm + 1e-6))
- *   hp[9]  = hp[8] * clip_coef                          (fp32 product: clip_coef == 1 gives hp[9] == hp[8] bit for bit)
- * g itself is not changed: vitpe_adamw_step with zero_grad bit 2 scales by hp[9].  Non-finite values follow the formula
+ *   hp[TOTAL_NORM] = hp[GRAD_SCALE] * sqrt(sum g[i]^2)      (the norm of the gradient AdamW uses, g * grad_scale)
+ *   hp[CLIP_COEF]  = min(1, hp[MAX_NORM] / (total_norm + 1e-6))
+ *   hp[CLIP_SCALE] = hp[GRAD_SCALE] * clip_coef      (fp32 product: clip_coef == 1 gives GRAD_SCALE's bits)
+ * g itself is not changed: vitpe_adamw_step with zero_grad bit 2 scales by hp[CLIP_SCALE].  Non-finite values follow the formula
  * (a NaN norm gives a NaN coefficient, as torch's clamp does).  partial: work buffer of n_partial >=
  * vitpe_grad_clip_blocks(n) floats, one per workgroup of the first launch, summed in fp64 in a fixed order by the
  * second.  The grid depends on n alone, so the result is the same bit for bit from run to run and from device to device.
@@ -553,13 +580,13 @@ int vitpe_grad_clip(const float* g, long long n, float* hp, float* partial, int 
 int vitpe_grad_clip_blocks(long long n);
 /* Exponential moving average of the flat fp32 parameters p [n] into e [n], one launch, elementwise:
  *   e[i] = fmaf(w, p[i] - e[i], e[i]),  w = 1.0f - d_t                         (all fp32; p is only read)
- *   d_t  = hp[13]                                                              (warmup == 0)
- *   d_t  = fminf(hp[13], (1.0f + t) / (10.0f + t)),  t = hp[5] - hp[14]        (warmup != 0: TF's num_updates rule)
- * hp[5] is AdamW's step counter, already advanced for this step (call it after vitpe_adamw_step); hp[14] its value when
- * the average was switched on.  hp[5], hp[13], hp[14] are only read; one lane stores d_t to hp[15].  The division is
+ *   d_t  = hp[EMA_DECAY]                                                       (warmup == 0)
+ *   d_t  = fminf(hp[EMA_DECAY], (1.0f + t) / (10.0f + t)),  t = hp[STEP] - hp[EMA_ORIGIN]   (warmup != 0: TF's num_updates rule)
+ * hp[STEP] is AdamW's step counter, already advanced for this step (call it after vitpe_adamw_step); hp[EMA_ORIGIN] its value
+ * when the average was switched on.  Those three are only read; one lane stores d_t to hp[EMA_DT].  The division is
  * correctly rounded.  p[i] == e[i] leaves e[i]'s bits (fmaf(w, 0, e) == e): a converged average is a fixed point.
  * p and e 16-byte aligned (16-byte loads and stores per lane, the n % 4 last elements one lane each; the grid is
- * vitpe_ema_blocks(n) workgroups of 256, grid-stride).  n == 0 launches nothing (hp[15] keeps its value).
+ * vitpe_ema_blocks(n) workgroups of 256, grid-stride).  n == 0 launches nothing (hp[EMA_DT] keeps its value).
  * hipErrorInvalidValue for NULL hp, NULL p / e with n > 0, n < 0, or a p / e that is not 16-byte aligned; nothing is
  * launched then.                                                                                                     */
 int vitpe_ema_update(const float* p, float* e, float* hp, long long n, int warmup, vitpe_stream_t stream);

@@ -1,4 +1,4 @@
-"""Plain numpy / float64 restatement of the weight EMA the train step keeps (vitpe_ema_update in csrc/ema.hip,
+"""Plain numpy / float64 restatement of the weight EMA the train step keeps (vitpe_ema_update in csrc/optim.hip,
 include/vitpe.h):  e' = e + w (p - e),  w = 1 - d_t,  d_t = decay or min(decay, (1 + t) / (10 + t)).  Shared by
 tests/test_ema_cpu.py (the reference is self-consistent) and tests/test_ema_gpu.py (the kernels and the engine against
 it).  No GPU and no vitpe import here."""

@@ -15,6 +15,10 @@ space-separated) and the SHA-256 of the canonical full trace.  Run as a script o
 
     python tests/engine_trace.py --dump DIR            full traces, one JSON file per configuration and sequence
     python tests/engine_trace.py --write-golden FILE   the golden (only ever from the commit BEFORE an engine refactor)
+    python tests/engine_trace.py --write-golden FILE --only NAME [NAME ...] --commit HASH
+                                                       record the named configurations alone and merge them into FILE: its
+                                                       other entries and its "recorded_from" stay as they are, each new
+                                                       entry carries its own "recorded_from"
 """
 import contextlib
 import ctypes
@@ -45,9 +49,11 @@ BATCH = 2
 
 
 def _cfg(geom="CIFAR", env=None, dtype="bf16", fuse_ln=None, extras=False, model=None, pe="rope-axial", depth=3,
-         dataset=False, probes=False):
+         dataset=False, probes=False, optim=None):
+    """optim: the optimizer-side options, {"clip": max_norm, "ema": (decay, warmup), "groups": vit_param_groups' keywords,
+    "sched": set_lr_schedule's arguments}, each applied through the engine's public method when present."""
     return dict(geom=geom, env=env or {}, dtype=dtype, fuse_ln=fuse_ln, extras=extras, model=model or {}, pe=pe, depth=depth,
-                dataset=dataset, probes=probes)
+                dataset=dataset, probes=probes, optim=optim or {})
 
 
 CONFIGS = {"cifar-bf16": _cfg(probes=True)}
@@ -68,6 +74,15 @@ for _pe in ("absolute", "relative", "polynomial", "rope-axial", "rope-mixed"):
     CONFIGS["pe-" + _pe] = _cfg(pe=_pe)
 CONFIGS["dataset-augment-clip"] = _cfg(dataset=True)
 CONFIGS["depth-1"] = _cfg(depth=1)
+# what runs between the backward and the next forward: schedule, clip, AdamW (plain or grouped), EMA, rng_advance
+_OPTIM_ALL = dict(clip=1.0, ema=(0.99, True), groups=dict(no_decay=True, layer_decay=0.75), sched=(1e-3, 40, 5, 1e-5))
+CONFIGS.update({
+    "optim-all": _cfg(optim=_OPTIM_ALL),
+    "optim-all-fp32": _cfg(dtype="fp32", optim=_OPTIM_ALL),      # no bf16 shadow: its pointer is null
+    "optim-extras-all": _cfg(extras=True, model=CONFIGS["extras-all"]["model"], optim=_OPTIM_ALL),
+    "optim-groups-only": _cfg(optim=dict(groups=_OPTIM_ALL["groups"])),
+    "optim-sched-ema": _cfg(optim=dict(ema=(0.99, False), sched=_OPTIM_ALL["sched"])),   # the ticked adamw_step path
+})
 
 
 def route_args(cfg):
@@ -162,6 +177,10 @@ def build_engine(cfg):
     from vitpe.data import ResidentDataset
     from vitpe.engine import TrainEngine
     from vitpe.vit import VisionTransformer
+    try:
+        from vitpe.optim import vit_param_groups
+    except ImportError:   # only for re-recording the optim-* goldens from 439e3f7, which keeps it in the engine's module
+        from vitpe.engine import vit_param_groups
     g = GEOMS[cfg["geom"]]
     torch.manual_seed(0)
     model = VisionTransformer(pos_encoding=cfg["pe"], depth=cfg["depth"], **g, **cfg["model"]).cuda()
@@ -178,6 +197,15 @@ def build_engine(cfg):
         eng.set_augment(4, True)
         eng.set_grad_clip(1.0)
         idx = torch.tensor([5, 2], device="cuda")
+    opt = cfg["optim"]
+    if "clip" in opt:
+        eng.set_grad_clip(opt["clip"])
+    if "ema" in opt:
+        eng.set_ema(*opt["ema"])
+    if "groups" in opt:
+        eng.set_param_groups(vit_param_groups(model, **opt["groups"]))
+    if "sched" in opt:
+        eng.set_lr_schedule(*opt["sched"])
     return eng, images, labels, idx
 
 
@@ -205,7 +233,12 @@ def _seq_probes(eng, images, labels, idx):
             fn()
 
 
-SEQUENCES = (("step", _seq_step), ("eval", _seq_eval), ("parts", _seq_parts), ("probes", _seq_probes))
+def _seq_ema(eng, images, labels, idx):
+    with eng.ema_weights():
+        _seq_eval(eng, images, labels, idx)
+
+
+SEQUENCES = (("step", _seq_step), ("eval", _seq_eval), ("parts", _seq_parts), ("probes", _seq_probes), ("ema", _seq_ema))
 
 
 def trace_config(name):
@@ -216,7 +249,7 @@ def trace_config(name):
         route = {f: bool(getattr(eng, f)) for f in ROUTE_FLAGS}
         traces = {}
         for seq, run in SEQUENCES:
-            if seq == "probes" and not cfg["probes"]:
+            if (seq == "probes" and not cfg["probes"]) or (seq == "ema" and "ema" not in cfg["optim"]):
                 continue
             with recording() as calls:
                 run(eng, images, labels, idx)
@@ -231,11 +264,18 @@ def main(argv):
     ap.add_argument("--dump", metavar="DIR", help="write every full trace to DIR/<config>.<sequence>.json")
     ap.add_argument("--write-golden", metavar="FILE", help="write the golden (names, hashes, route flags) to FILE")
     ap.add_argument("--commit", default="", help="hash of the commit the golden is recorded from (stored in it)")
+    ap.add_argument("--only", nargs="+", metavar="NAME", choices=list(CONFIGS),
+                    help="record these configurations alone; --write-golden then merges them into FILE")
     args = ap.parse_args(argv)
     golden = {"recorded_from": args.commit, "configs": {}}
-    for name in CONFIGS:
+    if args.only and args.write_golden:
+        with open(args.write_golden) as f:
+            golden = json.load(f)
+    for name in args.only or CONFIGS:
         route, traces = trace_config(name)
         entry = {"route": route, "sequences": {}}
+        if args.only:
+            entry["recorded_from"] = args.commit
         for seq, calls in traces.items():
             names, sha = digest(calls)
             entry["sequences"][seq] = {"names": " ".join(names), "sha256": sha}

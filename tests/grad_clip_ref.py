@@ -1,5 +1,5 @@
 """Plain numpy / float64 restatement of gradient clipping by global norm as the train step does it (vitpe_grad_clip in
-csrc/misc.hip, include/vitpe.h): torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2.0) on the gradient AdamW
+csrc/optim.hip, include/vitpe.h): torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2.0) on the gradient AdamW
 uses, g * gs (gs = hp[8]).  Shared by tests/test_grad_clip_cpu.py (the reference agrees with torch, the inputs
 discriminate) and tests/test_grad_clip_gpu.py (the kernels against it).  No GPU and no vitpe import here."""
 import numpy as np

@@ -310,3 +310,19 @@ def test_train_py_refuses_unsupported_geometries_up_front():
                 ["--pos_encoding", "polynomial", "--poly_degree", "9"]):
         with pytest.raises(SystemExit):
             T.get_args(bad)
+
+
+def test_hp_and_sched_slot_names_agree_in_header_kernels_and_python():
+    """enum vitpe_hp_slot / vitpe_sched_slot of include/vitpe.h are the layout; csrc/common.h (HP_*, SCHED_*) and
+    vitpe/_lib.py mirror them, and nothing else keeps the three copies equal."""
+    from vitpe import _lib
+    header = re.sub(r"/\*.*?\*/", " ", open(_lib.HEADER_PATH).read(), flags=re.S)
+    common = open(os.path.join(_lib.PKG_ROOT, "csrc", "common.h")).read()
+    for enum, prefix, count in (("vitpe_hp_slot", "HP_", 16), ("vitpe_sched_slot", "SCHED_", 8)):
+        body = re.search(r"enum\s+" + enum + r"\s*\{(.*?)\}", header, flags=re.S).group(1)
+        slots = {m.group(1): int(m.group(2)) for m in re.finditer(r"\bVITPE_(" + prefix + r"\w+)\s*=\s*(\d+)", body)}
+        assert slots[prefix + "COUNT"] == count == len(slots) - 1
+        assert sorted(v for k, v in slots.items() if k != prefix + "COUNT") == list(range(count))
+        mirrored = {m.group(1): int(m.group(2)) for m in re.finditer(r"(?<![A-Z_])(" + prefix + r"\w+)\s*=\s*(\d+)", common)}
+        assert mirrored == slots
+        assert {k: getattr(_lib, k) for k in slots} == slots

@@ -2,12 +2,14 @@
 symbols and their host-side argument checks, the host-only argument handling of TrainEngine.set_ema / ema_weights, and
 train.py's two flags."""
 import ctypes
+import functools
 import sys
 
 import numpy as np
 import pytest
 
 import ema_ref as R
+from optim_host import cpu_optimizer
 from vitpe import _lib
 
 
@@ -89,28 +91,38 @@ def test_new_symbols_in_header_and_library():
 
 
 # ------------------------------------------------------------------------------------------ TrainEngine, host side
-def _bare_engine():
-    from vitpe.engine import TrainEngine
-    return TrainEngine.__new__(TrainEngine)    # no device here: only what the methods do before they touch one
+class _HostEngine:
+    """TrainEngine's methods over a StepOptimizer alone: what they do before they touch the model or a device.  The stand-in
+    has `opt` and nothing else, so this only works for methods whose FIRST statement is their opt.guard / opt.needs_ema
+    call -- which is what these tests assert; a method that read anything else of the engine first would fail here with
+    an AttributeError, not pass."""
+
+    def __init__(self, opt):
+        self.opt = opt
+
+    def __getattr__(self, name):
+        from vitpe.engine import TrainEngine
+        return functools.partial(getattr(TrainEngine, name), self)
 
 
 def test_set_ema_argument_handling_without_a_device():
-    eng = _bare_engine()
+    from vitpe.optim import ema_value
+    opt, dropped = cpu_optimizer()
+    eng = _HostEngine(opt)
     for bad in (-0.1, 1.0, float("nan"), 1.5, float("inf"), -1e-9):
         with pytest.raises(_lib.VitpeError, match="set_ema"):
             eng.set_ema(bad)
         with pytest.raises(_lib.VitpeError, match="set_ema"):
             eng.set_ema(bad, warmup=True)
-    assert eng.ema_decay is None and eng.flat_e is None and eng.ema_warmup is False
+    assert opt.ema_decay is None and opt.flat_e is None and opt.ema_warmup is False
     # off -> off: nothing to allocate, nothing to drop, no device needed
-    eng.graph_fb = eng.graph_fb2 = eng.graph_opt = "captured"
     eng.set_ema(None)
     eng.set_ema(0)
     eng.set_ema(0.0, warmup=True)              # (a warm-up of nothing stays off)
-    assert eng.ema_decay is None and eng.ema_warmup is False and eng.graph_fb == "captured"
+    assert opt.ema_decay is None and opt.ema_warmup is False and dropped == []
     # the accepted values, as far as host logic goes
-    assert eng._ema_value(None) is None and eng._ema_value(0) is None and eng._ema_value(0.999) == 0.999
-    assert eng._ema_value(np.float32(0.5)) == 0.5
+    assert ema_value(None) is None and ema_value(0) is None and ema_value(0.999) == 0.999
+    assert ema_value(np.float32(0.5)) == 0.5
     # what needs the average refuses while it is off
     for call in (eng.reset_ema, eng.ema_state_dict, lambda: eng.load_ema_state_dict({})):
         with pytest.raises(_lib.VitpeError, match="EMA is off"):
@@ -121,8 +133,9 @@ def test_set_ema_argument_handling_without_a_device():
 
 
 def test_training_calls_refuse_inside_the_swapped_state():
-    eng = _bare_engine()
-    eng.ema_decay, eng._ema_swapped = 0.9, True          # as inside `with eng.ema_weights():`
+    opt, _ = cpu_optimizer()
+    opt.ema_decay, opt.ema_swapped = 0.9, True          # as inside `with eng.ema_weights():`
+    eng = _HostEngine(opt)
     for name, call in (("step", eng.step), ("step_indexed", lambda: eng.step_indexed(None)),
                        ("forward_backward", eng.forward_backward), ("capture", eng.capture),
                        ("set_ema", lambda: eng.set_ema(0.5)), ("reset_ema", eng.reset_ema)):

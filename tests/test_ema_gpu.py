@@ -1,4 +1,4 @@
-"""Weight EMA inside the train step: vitpe_ema_update / vitpe_ema_swap (csrc/ema.hip) against the float64 restatement of
+"""Weight EMA inside the train step: vitpe_ema_update / vitpe_ema_swap (csrc/optim.hip) against the float64 restatement of
 tests/ema_ref.py, then TrainEngine.set_ema / ema_weights / ema_state_dict eager, in captured graphs, on the extras route
 and from train.py --model_ema.
 
@@ -247,13 +247,13 @@ def _recurrence(e0, snaps, d):
 
 def test_engine_eager_fp32_follows_the_recurrence():
     eng = _engine(False)
-    assert eng.ema_decay is None and eng.flat_e is None
+    assert eng.opt.ema_decay is None and eng.opt.flat_e is None
     eng.step()                                            # one step before the average exists: hp[14] is not just zero
     eng.set_ema(0.9)
-    assert eng.ema_decay == 0.9 and eng.ema_warmup is False
-    assert eng.flat_e.dtype == torch.float32 and eng.flat_e.numel() == eng.n_flat and eng.flat_e.data_ptr() % 16 == 0
-    assert torch.equal(bits(eng.flat_e), bits(eng.flat_p))
-    e0, snaps = f64(eng.flat_e), []
+    assert eng.opt.ema_decay == 0.9 and eng.opt.ema_warmup is False
+    assert eng.opt.flat_e.dtype == torch.float32 and eng.opt.flat_e.numel() == eng.n_flat and eng.opt.flat_e.data_ptr() % 16 == 0
+    assert torch.equal(bits(eng.opt.flat_e), bits(eng.flat_p))
+    e0, snaps = f64(eng.opt.flat_e), []
     for _ in range(3):
         eng.step()
         snaps.append(f64(eng.flat_p))
@@ -262,14 +262,14 @@ def test_engine_eager_fp32_follows_the_recurrence():
     assert hp[5] == 4.0 and hp[14] == 1.0
     assert hp[13].tobytes() == np.float32(0.9).tobytes() == hp[15].tobytes()
     ref, bound = _recurrence(e0, snaps, hp[15])[-1]
-    fig = worst(f64(eng.flat_e) - ref, bound)
+    fig = worst(f64(eng.opt.flat_e) - ref, bound)
     moved = float(np.abs(ref - e0).max())
     print(f"eager fp32, 3 steps: worst |err| / summed bound {fig:.3f}; the average moved by up to {moved:.3e}")
     assert fig <= 1.0 and moved > 0
-    assert not np.array_equal(f64(eng.flat_e), snaps[-1])                 # the average, not a copy of the parameters
+    assert not np.array_equal(f64(eng.opt.flat_e), snaps[-1])                 # the average, not a copy of the parameters
     # reset_ema: a copy of the parameters again, the warm-up's origin re-based
     eng.reset_ema()
-    assert torch.equal(bits(eng.flat_e), bits(eng.flat_p)) and float(eng.hp[14]) == 4.0
+    assert torch.equal(bits(eng.opt.flat_e), bits(eng.flat_p)) and float(eng.hp[14]) == 4.0
 
 
 @pytest.mark.parametrize("extras", [False, True])
@@ -285,7 +285,7 @@ def test_engine_graph_replay_averages_like_the_eager_engine(extras):
     after = []
     for step in range(3):
         eager.step(); graph.step()
-        after.append(f64(graph.flat_e))
+        after.append(f64(graph.opt.flat_e))
         if step == 0:
             # the capture's warm-up (two real optimizer steps, then restored) leaves no trace: ONE application of the
             # recurrence leads from the initial copy to this step's parameters
@@ -297,7 +297,7 @@ def test_engine_graph_replay_averages_like_the_eager_engine(extras):
             assert float(graph.hp[5]) == 1.0 and float(graph.hp[14]) == 0.0
     assert graph.graph_fb is not None and eager.graph_fb is None
     assert not np.array_equal(after[1], after[0]) and not np.array_equal(after[2], after[1])    # it moves between replays
-    err = rel_err(graph.flat_e.cpu(), eager.flat_e.cpu())
+    err = rel_err(graph.opt.flat_e.cpu(), eager.opt.flat_e.cpu())
     err_p = rel_err(graph.flat_p.cpu(), eager.flat_p.cpu())
     print(f"extras {extras}: graph vs eager after 3 steps: rel err of the average {err:.3e}, of the parameters {err_p:.3e}")
     assert err < 1e-5
@@ -311,14 +311,14 @@ def test_engine_graph_replay_averages_like_the_eager_engine(extras):
     assert graph.graph_fb is fb and float(graph.hp[5]) == 4.0 and graph.hp[15].item() == float(np.float32(0.95))
     # the warm-up switch is compiled into the launch: changing it drops the graph
     graph.set_ema(0.95, warmup=True)
-    assert graph.graph_fb is None and graph.ema_warmup is True
+    assert graph.graph_fb is None and graph.opt.ema_warmup is True
     graph.step()
     assert ulps(graph.hp[15].item(), R.warmup_decay(0.95, 5)) <= 1 and graph.hp[15].item() < 0.5
     # off: the graphs are dropped, the next step captures anew and nothing writes hp[13..15] or the former buffer
-    fb, former = graph.graph_fb, graph.flat_e
+    fb, former = graph.graph_fb, graph.opt.flat_e
     kept, before = former.clone(), graph.hp.clone()
     graph.set_ema(None)
-    assert graph.graph_fb is None and graph.ema_decay is None and graph.flat_e is None
+    assert graph.graph_fb is None and graph.opt.ema_decay is None and graph.opt.flat_e is None
     graph.step()
     torch.cuda.synchronize()
     assert graph.graph_fb is not None and graph.graph_fb is not fb and float(graph.hp[5]) == 6.0
@@ -338,8 +338,9 @@ def test_ema_weights_swaps_the_average_in_and_restores_every_bit(dt):
     fb = eng.graph_fb
     names = ["flat_p", "flat_e", "_shadow_flat"] + (["flat_s"] if dt == torch.bfloat16 else [])
     assert (eng.flat_s is not None) == (dt == torch.bfloat16)
-    clones = {k: getattr(eng, k).clone() for k in names}
-    ptrs = {k: getattr(eng, k).data_ptr() for k in names}
+    buf = lambda k: getattr(eng.opt if k == "flat_e" else eng, k)   # noqa: E731  (the average is the optimizer's)
+    clones = {k: buf(k).clone() for k in names}
+    ptrs = {k: buf(k).data_ptr() for k in names}
     images = eng.images.clone()
     sd_out = eng.ema_state_dict()
     params = dict(eng.model.named_parameters())
@@ -349,12 +350,12 @@ def test_ema_weights_swaps_the_average_in_and_restores_every_bit(dt):
 
     def restored():
         torch.cuda.synchronize()
-        return (all(torch.equal(bits(getattr(eng, k)), bits(clones[k])) for k in names)
-                and all(getattr(eng, k).data_ptr() == ptrs[k] for k in names) and eng._ema_swapped is False)
+        return (all(torch.equal(bits(buf(k)), bits(clones[k])) for k in names)
+                and all(buf(k).data_ptr() == ptrs[k] for k in names) and eng.opt.ema_swapped is False)
 
     with eng.ema_weights() as inside:
         assert inside is eng
-        assert torch.equal(bits(eng.flat_p), bits(clones["flat_e"])) and torch.equal(bits(eng.flat_e), bits(clones["flat_p"]))
+        assert torch.equal(bits(eng.flat_p), bits(clones["flat_e"])) and torch.equal(bits(eng.opt.flat_e), bits(clones["flat_p"]))
         logits = eng.forward_only(images).clone()
         sd_in = eng.model.state_dict()
         assert list(sd_in) == list(sd_out) and all(torch.equal(bits(sd_in[k]), bits(sd_out[k])) for k in sd_out)
@@ -377,23 +378,23 @@ def test_ema_weights_swaps_the_average_in_and_restores_every_bit(dt):
     assert not torch.equal(bits(logits), bits(eng.forward_only(images)))                    # ... and not the weights' own
     # load_ema_state_dict is ema_state_dict's inverse
     other.set_ema(0.5)
-    other.flat_e.mul_(2.0)                                # (the padding between parameters stays zero, as in eng.flat_e)
+    other.opt.flat_e.mul_(2.0)                                # (the padding between parameters stays zero, as in eng.opt.flat_e)
     p_before = other.flat_p.clone()
     other.load_ema_state_dict(sd_out)
-    assert torch.equal(bits(other.flat_e), bits(eng.flat_e)) and torch.equal(bits(other.flat_p), bits(p_before))
+    assert torch.equal(bits(other.opt.flat_e), bits(eng.opt.flat_e)) and torch.equal(bits(other.flat_p), bits(p_before))
     with pytest.raises(VitpeError, match="load_ema_state_dict"):
         other.load_ema_state_dict({k: v for k, v in sd_out.items() if k != "cls_token"})
     # an exception raised inside still restores
     with pytest.raises(ZeroDivisionError):
         with eng.ema_weights():
-            assert eng._ema_swapped is True
+            assert eng.opt.ema_swapped is True
             1 / 0
     assert restored()
     # ... and training goes on through the same captured graph
     eng.step()
     torch.cuda.synchronize()
     assert eng.graph_fb is fb and float(eng.hp[5]) == 4.0
-    assert not torch.equal(bits(eng.flat_e), bits(clones["flat_e"]))
+    assert not torch.equal(bits(eng.opt.flat_e), bits(clones["flat_e"]))
 
 
 def test_ema_switched_off_again_is_inert():
@@ -415,9 +416,9 @@ def test_ema_switched_off_again_is_inert():
     plain, toggled = _engine(True, eps=1e-3), _engine(True, eps=1e-3)
     assert float(plain.hp[3]) == float(np.float32(1e-3))
     toggled.set_ema(0.99)
-    former = toggled.flat_e
+    former = toggled.opt.flat_e
     toggled.set_ema(None)
-    assert toggled.flat_e is None and toggled.ema_decay is None
+    assert toggled.opt.flat_e is None and toggled.opt.ema_decay is None
     kept = former.clone()
     for _ in range(3):
         plain.step(); toggled.step()
@@ -461,10 +462,10 @@ def test_train_py_model_ema_evaluates_and_checkpoints_the_average(tmp_path, monk
                      str(tmp_path / "ckpt")])
     assert len(seen) == 1 and seen[0][1:] == (0.9, True)
     eng = seen[0][0]
-    assert eng.flat_e is not None and eng.flat_e.numel() == eng.n_flat and eng.ema_decay == 0.9 and eng.ema_warmup
-    assert eng._ema_swapped is False and float(eng.hp[5]) == 3.0 and float(eng.hp[14]) == 0.0
+    assert eng.opt.flat_e is not None and eng.opt.flat_e.numel() == eng.n_flat and eng.opt.ema_decay == 0.9 and eng.opt.ema_warmup
+    assert eng.opt.ema_swapped is False and float(eng.hp[5]) == 3.0 and float(eng.hp[14]) == 0.0
     assert ulps(eng.hp[15].item(), R.warmup_decay(0.9, 3)) <= 1
-    assert not torch.equal(bits(eng.flat_e), bits(eng.flat_p))
+    assert not torch.equal(bits(eng.opt.flat_e), bits(eng.flat_p))
     logs = list((tmp_path / "logs").glob("mnist_rope-axial_*.csv"))
     assert len(logs) == 1
     rows = list(csv.reader(logs[0].read_text().splitlines()))

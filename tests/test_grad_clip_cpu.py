@@ -1,6 +1,6 @@
 """Gradient clipping by global norm -- what can be checked without a GPU: the float64 reference of tests/grad_clip_ref.py
 against torch.nn.utils.clip_grad_norm_, that the kernel tests' inputs tell every wrong coefficient from the right one, the
-new C symbols and their host-side argument checks, and the host-only behaviour of TrainEngine.set_grad_clip / grad_norm."""
+new C symbols and their host-side argument checks, and the host-only behaviour of set_grad_clip / grad_norm (vitpe/optim.py)."""
 import ctypes
 import sys
 
@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import grad_clip_ref as R
+from optim_host import cpu_optimizer
 from vitpe import _lib
 
 
@@ -115,27 +116,21 @@ def test_new_symbols_in_header_and_library():
     assert h.vitpe_grad_clip(None, 0, None, None, 0, None) == 1          # n == 0 still writes hp
 
 
-def _bare_engine():
-    from vitpe.engine import TrainEngine
-    return TrainEngine.__new__(TrainEngine)    # no device here: only what the two methods do before they touch one
-
-
 def test_set_grad_clip_refuses_bad_values_and_grad_norm_needs_the_clip_on():
-    eng = _bare_engine()
+    opt, dropped = cpu_optimizer()
     for bad in (-1, -1e-9, float("nan"), float("inf"), float("-inf")):
         with pytest.raises(_lib.VitpeError, match="set_grad_clip"):
-            eng.set_grad_clip(bad)
-    assert eng.clip_max_norm is None
+            opt.set_grad_clip(bad)
+    assert opt.clip_max_norm is None
     with pytest.raises(_lib.VitpeError, match="clipping is off"):
-        eng.grad_norm()
+        opt.grad_norm()
     # off -> off: nothing to allocate, nothing to drop, no device needed
-    eng.graph_fb = eng.graph_fb2 = eng.graph_opt = "captured"
-    eng.set_grad_clip(None)
-    eng.set_grad_clip(0)
-    eng.set_grad_clip(0.0)
-    assert eng.clip_max_norm is None and eng.graph_fb == "captured"
+    opt.set_grad_clip(None)
+    opt.set_grad_clip(0)
+    opt.set_grad_clip(0.0)
+    assert opt.clip_max_norm is None and dropped == []
     with pytest.raises(_lib.VitpeError, match="clipping is off"):
-        eng.grad_norm()
+        opt.grad_norm()
 
 
 def test_train_py_clip_grad_flag():

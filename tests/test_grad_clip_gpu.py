@@ -1,5 +1,5 @@
 """Gradient clipping by global norm inside the train step: vitpe_grad_clip (grad_sqnorm_kernel + grad_clip_finalize_kernel,
-csrc/misc.hip) and the hp[9] route of adamw_kernel against the float64 restatements of tests/grad_clip_ref.py and
+csrc/optim.hip) and the hp[9] route of adamw_kernel against the float64 restatements of tests/grad_clip_ref.py and
 tests/train_state_ref.py, then TrainEngine.set_grad_clip / grad_norm eager, in captured graphs, on the extras route and
 from train.py --clip_grad.
 
@@ -226,7 +226,7 @@ def test_engine_eager_fp32_clips_to_half_the_norm():
     norm_ref, _ = R.clip_ref(f64(g), gs, 1.0)
     assert norm_ref > 0
     eng.set_grad_clip(0.5 * norm_ref)
-    assert eng._clip_partial.numel() == K_blocks(eng.n_flat)
+    assert eng.opt._clip_partial.numel() == K_blocks(eng.n_flat)
     p0, m0, v0 = f64(eng.flat_p), f64(eng.flat_m), f64(eng.flat_v)
     eng._optimizer()
     torch.cuda.synchronize()
@@ -274,7 +274,7 @@ def test_engine_graph_replay_clips_like_the_eager_engine(extras):
     norms = []
     for eng in (eager, graph):
         eng.set_grad_clip(max_norm)
-        assert eng.clip_max_norm == max_norm and eng.graph_fb is None
+        assert eng.opt.clip_max_norm == max_norm and eng.graph_fb is None
     for step in range(3):
         eager.step(); graph.step()
         norms.append((eager.grad_norm(), graph.grad_norm()))
@@ -296,7 +296,7 @@ def test_engine_graph_replay_clips_like_the_eager_engine(extras):
     assert ulps(float(graph.hp[11]), R.coef_from_norm(graph.hp[10].item(), graph.hp[12].item())) <= 2
     # off: the graphs are dropped, the next step captures anew and nothing writes hp[9..11] any more
     graph.set_grad_clip(None)
-    assert graph.graph_fb is None and graph.clip_max_norm is None
+    assert graph.graph_fb is None and graph.opt.clip_max_norm is None
     before = graph.hp.cpu()
     graph.step()
     torch.cuda.synchronize()
@@ -324,7 +324,7 @@ def test_train_py_clip_grad_reaches_the_engine(tmp_path, monkeypatch):
             "--log_dir", str(tmp_path / "logs"), "--ckpt_dir", str(tmp_path / "ckpt")])
     assert len(seen) == 1 and seen[0][1] == 1.0
     eng = seen[0][0]
-    assert eng.clip_max_norm == 1.0 and float(eng.hp[12]) == 1.0 and float(eng.hp[5]) == 3.0
+    assert eng.opt.clip_max_norm == 1.0 and float(eng.hp[12]) == 1.0 and float(eng.hp[5]) == 3.0
     assert eng.grad_norm() > 0.0 and 0.0 < float(eng.hp[11]) <= 1.0
     logs = list((tmp_path / "logs").glob("mnist_rope-axial_*.csv"))
     assert len(logs) == 1

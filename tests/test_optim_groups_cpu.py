@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import optim_groups_ref as R
+from optim_host import cpu_optimizer
 import train_state_ref as TS
 from vitpe import _lib
 
@@ -111,7 +112,7 @@ def test_blocks_rule_and_maps():
     for o, k, grp in zip(offs, numels, group_of):
         assert np.all(eg[o:o + k] == grp)
     # the engine's builder agrees, and the padding behind the last parameter keeps group 0
-    from vitpe.engine import param_granule_map
+    from vitpe.optim import param_granule_map
     got = param_granule_map([(o, k, grp) for o, k, grp in zip(offs, numels, group_of)], n_flat + 16)
     assert got.dtype == np.uint8 and got.tolist() == gid.tolist() + [0, 0]
 
@@ -137,7 +138,7 @@ def _expected_no_decay(model):
 @pytest.mark.parametrize("qkv_bias", [False, True])
 @pytest.mark.parametrize("mode", PE_MODES)
 def test_vit_param_groups_follow_the_recipe(mode, qkv_bias):
-    from vitpe.engine import torch_param_groups, vit_layer_id, vit_param_groups
+    from vitpe.optim import torch_param_groups, vit_layer_id, vit_param_groups
     model = _cpu_model(mode, qkv_bias)
     named = dict(model.named_parameters())
     depth = len(model.blocks)
@@ -188,7 +189,7 @@ def test_vit_param_groups_follow_the_recipe(mode, qkv_bias):
 
 def test_map_of_a_model_layout_carries_every_parameters_group():
     from vitpe import ddp
-    from vitpe.engine import param_granule_map, vit_param_groups
+    from vitpe.optim import param_granule_map, vit_param_groups
     from vitpe.route import ALIGN
     assert ALIGN == R.GRANULE
     model = _cpu_model("rope-mixed", qkv_bias=True, depth=2)
@@ -242,19 +243,14 @@ def test_new_symbols_in_header_and_library():
 
 
 # ------------------------------------------------------------------------------------------ TrainEngine, host side
-def _bare_engine():
-    from vitpe.engine import TrainEngine
-    return TrainEngine.__new__(TrainEngine)    # no device here: only what the methods do before they touch one
-
-
 def test_set_param_groups_argument_handling_without_a_device():
-    eng = _bare_engine()
+    from vitpe.optim import group_scales
+    w, b = torch.nn.Parameter(torch.zeros(4, 4)), torch.nn.Parameter(torch.zeros(4))
+    eng, dropped = cpu_optimizer({id(w): 0})                          # the model's parameters, as _build_flat records them
     assert eng.param_groups is None and eng._gid is None and eng._gtab is None
-    eng.graph_fb = eng.graph_fb2 = eng.graph_opt = "captured"
     eng.set_param_groups(None)
     eng.set_param_groups([])
-    assert eng.param_groups is None and eng.graph_fb == "captured"     # off -> off: nothing dropped, no device needed
-    w, b = torch.nn.Parameter(torch.zeros(4, 4)), torch.nn.Parameter(torch.zeros(4))
+    assert eng.param_groups is None and dropped == []                  # off -> off: nothing dropped, no device needed
     for key in ("lr_scale", "weight_decay_scale"):
         for bad in (-0.1, float("nan"), float("inf"), -1e-9, "x", None):
             with pytest.raises(_lib.VitpeError, match="set_param_groups: " + key):
@@ -269,20 +265,19 @@ def test_set_param_groups_argument_handling_without_a_device():
         eng.set_param_groups([[w]])
     with pytest.raises(_lib.VitpeError, match="at most 255"):
         eng.set_param_groups([{"params": []} for _ in range(256)])
-    eng._off = {id(w): 0}                                              # the model's parameters, as _build_flat records them
     with pytest.raises(_lib.VitpeError, match="not one of the model's"):
         eng.set_param_groups([{"params": [w]}, {"params": [b], "weight_decay_scale": 0.0}])
-    assert eng.param_groups is None and eng.graph_fb == "captured"
-    assert eng._group_scales([{"params": [w], "lr_scale": np.float32(0.5)}, {"params": (b,), "weight_decay_scale": 0}]) == \
+    assert eng.param_groups is None and dropped == []
+    assert group_scales([{"params": [w], "lr_scale": np.float32(0.5)}, {"params": (b,), "weight_decay_scale": 0}]) == \
         [([w], 0.5, 1.0), ([b], 1.0, 0.0)]
 
 
 def test_set_lr_schedule_argument_handling_without_a_device():
-    eng = _bare_engine()
+    from vitpe.optim import sched_values
+    eng, dropped = cpu_optimizer()
     assert eng.lr_sched is None and eng._sched is None
-    eng.graph_fb = eng.graph_fb2 = eng.graph_opt = "captured"
     eng.set_lr_schedule(None)
-    assert eng.lr_sched is None and eng.graph_fb == "captured"
+    assert eng.lr_sched is None and dropped == []
     good = dict(base_lr=1e-3, total_steps=40, warmup_steps=5, min_lr=0.0, warmup_factor=0.01, done=0)
     bad = [dict(total_steps=5), dict(total_steps=4), dict(total_steps=0), dict(warmup_steps=-1), dict(warmup_factor=0.0),
            dict(warmup_factor=1.5), dict(warmup_factor=float("nan")), dict(min_lr=-1e-9), dict(min_lr=2e-3),
@@ -291,14 +286,14 @@ def test_set_lr_schedule_argument_handling_without_a_device():
     for over in bad:
         with pytest.raises(_lib.VitpeError, match="set_lr_schedule"):
             eng.set_lr_schedule(**dict(good, **over))
-    assert eng.lr_sched is None and eng._sched is None and eng.graph_fb == "captured"
-    assert eng._sched_values(**good) == (1e-3, 0.0, 5, 40, 0.01, 0)
-    assert eng._sched_values(3e-4, 17, 0, 1e-5, 1.0, 3) == (3e-4, 1e-5, 0, 17, 1.0, 3)
-    assert eng._sched_values(None, 0, 0, 0.0, 1e-3, 0) is None
+    assert eng.lr_sched is None and eng._sched is None and dropped == []
+    assert sched_values(**good) == (1e-3, 0.0, 5, 40, 0.01, 0)
+    assert sched_values(3e-4, 17, 0, 1e-5, 1.0, 3) == (3e-4, 1e-5, 0, 17, 1.0, 3)
+    assert sched_values(None, 0, 0, 0.0, 1e-3, 0) is None
 
 
 def test_set_lr_refuses_under_a_schedule():
-    eng = _bare_engine()
+    eng, _ = cpu_optimizer()
     eng.lr_sched = (1e-3, 0.0, 5, 40, 0.01, 0)           # as after set_lr_schedule(1e-3, 40, 5)
     with pytest.raises(_lib.VitpeError, match="set_lr: a per-step schedule is on"):
         eng.set_lr(1e-4)

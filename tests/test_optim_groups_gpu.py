@@ -321,7 +321,7 @@ def _floors(bm, bv, m_ref, v_ref):
 
 def _host_map(eng, groups):
     """the map and table set_param_groups must have built, restated from the engine's offsets"""
-    from vitpe.engine import param_granule_map
+    from vitpe.optim import param_granule_map
     spans = [(eng._off[id(p)], p.numel(), k) for k, g in enumerate(groups, start=1) for p in g["params"]]
     table = [(1.0, 1.0)] + [(g["lr_scale"], g["weight_decay_scale"]) for g in groups]
     return param_granule_map(spans, eng.n_flat), table
@@ -329,13 +329,13 @@ def _host_map(eng, groups):
 
 @pytest.mark.parametrize("variant", ["plain", "clip", "extras"])
 def test_engine_eager_fp32_updates_every_group_with_its_own_rates(variant):
-    from vitpe.engine import vit_param_groups
+    from vitpe.optim import vit_param_groups
     eng = _engine(False, extras=(variant == "extras"))
     groups = vit_param_groups(eng.model, True, 0.75)
     eng.set_param_groups(groups)
     gid, table = _host_map(eng, groups)
-    assert np.array_equal(eng._gid.cpu().numpy(), gid) and eng._gid.dtype == torch.uint8
-    assert np.array_equal(eng._gtab.cpu().numpy(), np.array(table, dtype=np.float32))
+    assert np.array_equal(eng.opt._gid.cpu().numpy(), gid) and eng.opt._gid.dtype == torch.uint8
+    assert np.array_equal(eng.opt._gtab.cpu().numpy(), np.array(table, dtype=np.float32))
     assert len(table) == 1 + len(groups) and len({t for t in table}) >= 7      # 4 layer ids x decay or not
     eng.forward_backward()
     if variant == "clip":
@@ -405,7 +405,7 @@ def test_engine_captured_bf16_follows_the_schedule_and_the_groups():
         fbs.append(eng.graph_fb)
         eng.set_param_groups(groups_of(eng, 0.25))
         assert eng.graph_fb is fbs[-1]
-        assert eng._gtab.cpu().tolist() == [[1.0, 1.0], [0.0, 0.0], [0.25, 1.0]]
+        assert eng.opt._gtab.cpu().tolist() == [[1.0, 1.0], [0.0, 0.0], [0.25, 1.0]]
 
     p_start = graph.flat_p.clone()
     lrs_e, ps_e = _drive(eager, groups_of(eager), 8, scale_at=(4, rescale))
@@ -419,7 +419,7 @@ def test_engine_captured_bf16_follows_the_schedule_and_the_groups():
         print(f"step {j}: lr graph {lrs_g[j]!r} eager {lrs_e[j]!r} reference {ref!r}")
         assert ulps(lrs_g[j], ref) <= 1 and ulps(lrs_e[j], ref) <= 1
     assert lrs_g[5] != lrs_g[4] and lrs_g[6] == lrs_g[7] == float(np.float32(MIN_LR))
-    assert float(graph.hp[5]) == 8.0 and float(graph._sched[6]) == lrs_g[7]
+    assert float(graph.hp[5]) == 8.0 and float(graph.opt._sched[6]) == lrs_g[7]
     # the frozen group keeps its bits over all 8 steps; the others move at every step
     head_span = [(graph._off[id(p)], p.numel()) for n, p in graph.model.named_parameters() if n.startswith("head.")]
     other = graph.model.blocks[0].mlp.fc1.weight
@@ -456,7 +456,7 @@ def test_engine_captured_bf16_follows_the_schedule_and_the_groups():
     graph.step()
     assert graph.graph_fb is fb and ulps(graph.current_lr(), R.schedule_ref(3, float(np.float32(2e-3)), 0.0, 0, 10, 1e-3)) <= 1
     graph.set_lr_schedule(None)
-    assert graph.graph_fb is None and graph.lr_sched is None
+    assert graph.graph_fb is None and graph.opt.lr_sched is None
     graph.set_lr(5e-4)
     graph.step()
     assert graph.current_lr() == float(np.float32(5e-4)) and float(graph.hp[5]) == 10.0
@@ -467,11 +467,11 @@ def test_capture_leaves_the_schedule_where_it_found_it():
     eng.step()                                              # a counter that is not just zero
     eng.set_lr_schedule(1e-3, 6, warmup_steps=2, warmup_factor=0.1, done=1)
     assert eng.graph_fb is None
-    hp_before, sched_before = eng.hp.clone(), eng._sched.clone()
+    hp_before, sched_before = eng.hp.clone(), eng.opt._sched.clone()
     assert float(sched_before[5]) == 0.0
     eng.capture()
     torch.cuda.synchronize()
-    assert same_bits(eng.hp, hp_before) and same_bits(eng._sched, sched_before)
+    assert same_bits(eng.hp, hp_before) and same_bits(eng.opt._sched, sched_before)
     eng.step()
     assert float(eng.hp[5]) == 2.0
     assert ulps(eng.current_lr(), R.schedule_ref(1, float(np.float32(1e-3)), 0.0, 2, 6, float(np.float32(0.1)))) <= 1
@@ -489,15 +489,15 @@ def test_groups_and_schedule_switched_off_again_are_inert():
     757 .. 1737 elements of flat_p after 2 steps in 9 pairs out of 9, so nothing could be told from bits there.  At 1, 2
     and 4 images they agreed in every bit in 12 pairs out of 12 (bf16, depth 1 and 2).  The test carries its own
     control: a second untouched engine must agree with the first, else the comparison says nothing and fails as such."""
-    from vitpe.engine import vit_param_groups
+    from vitpe.optim import vit_param_groups
     plain, control, toggled = (_engine(True, dt=torch.bfloat16, B=B_INERT) for _ in range(3))
     toggled.set_param_groups(vit_param_groups(toggled.model, True, 0.75))
     toggled.set_lr_schedule(1e-3, 6, warmup_steps=2)
     hp0 = toggled.hp.clone()
     toggled.set_param_groups(None)
     toggled.set_lr_schedule(None)
-    assert toggled.param_groups is None and toggled._gid is None and toggled._gtab is None
-    assert toggled.lr_sched is None and toggled._sched is None and same_bits(toggled.hp, hp0) and same_bits(plain.hp, hp0)
+    assert toggled.opt.param_groups is None and toggled.opt._gid is None and toggled.opt._gtab is None
+    assert toggled.opt.lr_sched is None and toggled.opt._sched is None and same_bits(toggled.hp, hp0) and same_bits(plain.hp, hp0)
     for _ in range(2):
         plain.step(); control.step(); toggled.step()
     torch.cuda.synchronize()

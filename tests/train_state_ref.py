@@ -1,5 +1,5 @@
 """Plain numpy / float64 restatements of what a training step leaves behind: the AdamW update (adamw_kernel in
-csrc/misc.hip) and the seven destination layouts of refresh_shadows_kernel (kinds 0-6, include/vitpe.h).  Shared by
+csrc/optim.hip) and the seven destination layouts of refresh_shadows_kernel (kinds 0-6, include/vitpe.h).  Shared by
 tests/test_train_state_cpu.py (the references are right, the inputs discriminate) and tests/test_train_state_gpu.py
 (the kernels against them).  No GPU and no vitpe import here."""
 import math

@@ -4,7 +4,7 @@
 kernels: on flat buffers of the two model sizes -- the default CIFAR model (32 / 4, d 192, depth 6) and ViT-B/16
          (bench.py --config imnet: 224 / 16, d 768, depth 12): `adamw` = vitpe_adamw_step as the engine launches it (bf16
          flat copy, zero_grad, the step counter ticked by the head kernel: 34 B / element -- p, g, m, v in and out, the
-         bf16 copy out; csrc/misc.hip is untouched, so this is the kernel every earlier commit built), `groups` =
+         bf16 copy out), `groups` =
          vitpe_adamw_step_groups on the same operands with 4 groups (the (lr, wd) scales of the kernel test, spans of
          1 / 2 / 33 / 5 granules repeating: + 1 B per 8 elements), `groups1` = the same with every scale 1 (what the map
          costs without divergent rates), `sched` = vitpe_lr_schedule alone; rotating over a ring of operand sets (4 / 2
@@ -125,7 +125,8 @@ def kernels(name, ring, iters):
 def steps(name, B, iters, reps=5):
     """ONE engine, groups + schedule switched off and on in turn (each switch re-captures the step): the same buffers at
     the same addresses in both states -- two engines of this geometry differ by more than the update costs."""
-    from vitpe.engine import TrainEngine, vit_param_groups
+    from vitpe.engine import TrainEngine
+    from vitpe.optim import vit_param_groups
     g = torch.Generator(device="cuda").manual_seed(1)
     S = GEOM[name]["img_size"]
     images = torch.randn(B, 3, S, S, generator=g, device="cuda")

@@ -330,7 +330,7 @@ def main(argv=None):
     if use_ema:   # after the broadcast: the average starts from the parameters every rank trains
         engine.set_ema(args.model_ema, warmup=args.model_ema_warmup)
     if args.no_decay_norm_bias or args.layer_decay > 0:   # every rank builds the same map
-        from vitpe.engine import vit_param_groups
+        from vitpe.optim import vit_param_groups
         engine.set_param_groups(vit_param_groups(model, no_decay=args.no_decay_norm_bias, layer_decay=args.layer_decay or None))
     per_step = args.warmup_epochs > 0 or args.lr_per_step
     if per_step:   # linear warm-up + cosine, stepped by the captured step itself: one schedule over the whole run

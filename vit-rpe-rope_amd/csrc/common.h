@@ -305,6 +305,23 @@ VITPE_DEV void gelu_erf_grad_mul_x8(float* v, const float* uv) {
 // positional-encoding modes (include/vitpe.h VITPE_PE_*)
 enum { PE_NONE = 0, PE_ABSOLUTE = 1, PE_RELATIVE = 2, PE_POLY = 3, PE_ROPE_AXIAL = 4, PE_ROPE_MIXED = 5 };
 
+// slots of the optimizer's two device blocks (include/vitpe.h vitpe_hp_slot / vitpe_sched_slot, which say who writes what;
+// tests/test_abi_and_host_cpu.py keeps the three copies equal)
+enum { HP_LR = 0, HP_BETA1 = 1, HP_BETA2 = 2, HP_EPS = 3, HP_WEIGHT_DECAY = 4, HP_STEP = 5, HP_BC1 = 6, HP_BC2 = 7,
+       HP_GRAD_SCALE = 8, HP_CLIP_SCALE = 9, HP_TOTAL_NORM = 10, HP_CLIP_COEF = 11, HP_MAX_NORM = 12, HP_EMA_DECAY = 13,
+       HP_EMA_ORIGIN = 14, HP_EMA_DT = 15, HP_COUNT = 16 };
+enum { SCHED_BASE_LR = 0, SCHED_MIN_LR = 1, SCHED_WARMUP = 2, SCHED_TOTAL = 3, SCHED_START_FACTOR = 4, SCHED_ORIGIN = 5,
+       SCHED_LAST_LR = 6, SCHED_SPARE = 7, SCHED_COUNT = 8 };
+
+// The optimizer's step counter and bias corrections, one lane: adamw_tick_kernel (optim.hip) and the hp_tick branch of the
+// head's backward (misc.hip) both run this.
+VITPE_DEV void adamw_tick(float* hp) {
+  const float step = hp[HP_STEP] + 1.0f;
+  hp[HP_STEP] = step;
+  hp[HP_BC1] = 1.0f - powf(hp[HP_BETA1], step);
+  hp[HP_BC2] = 1.0f - powf(hp[HP_BETA2], step);
+}
+
 // Deterministic sum of R partial rows (rotary.hip): part [R][2L] fp32, dst0[i] += sum_r part[r][i], dst1[i] += sum_r
 // part[r][L + i] (a null destination is skipped), in a fixed order -- slices of rows summed in place into their first
 // row, then the slices in order.  No float atomics: the result is bit-reproducible.  Clobbers part.

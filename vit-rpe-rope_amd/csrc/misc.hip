@@ -1,5 +1,5 @@
 // Patch-embed unfold, positional-encoding table builders, stand-alone rotary apply, classifier
-// head + cross-entropy, fused AdamW with weight shadows, and the primitive self-tests.
+// head + cross-entropy, the weight shadows, and the primitive self-tests.
 #include "common.h"
 #include "augment.h"
 
@@ -515,11 +515,7 @@ __global__ void head_bwd_params_kernel(const float* __restrict__ dlogits, const 
                                        int bchunk, const float* __restrict__ per_image, float* out2, float* metric_acc,
                                        float* hp_tick) {
   if (hp_tick != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
-    // the optimizer's step counter and bias corrections (adamw_tick_kernel's work: one launch less per step)
-    const float step = hp_tick[5] + 1.0f;
-    hp_tick[5] = step;
-    hp_tick[6] = 1.0f - powf(hp_tick[1], step);
-    hp_tick[7] = 1.0f - powf(hp_tick[2], step);
+    adamw_tick(hp_tick);   // adamw_tick_kernel's work (optim.hip): one launch less per step
   }
   if (per_image != nullptr && blockIdx.x == 0 && blockIdx.y == 0) {
     __shared__ float sl[256], sc[256];
@@ -583,103 +579,6 @@ __global__ void embed_bwd_kernel(const T* __restrict__ dtok, float* dcls, float*
   else if (dape) atomicAdd(dape + (size_t)(n - 1) * D + d, s);
 }
 
-// ---------------------------------------------------------------------------------------
-// Fused AdamW over the flat fp32 parameter / gradient / moment buffers (train.py:195:
-// one param group, decoupled weight decay on everything) + bf16 weight shadow + grad reset.
-// hp (device): [0]=lr [1]=beta1 [2]=beta2 [3]=eps [4]=weight_decay [5]=step [6]=bc1 [7]=bc2 [8]=grad_scale
-// [9]=grad_scale * clip_coef [10]=total_norm [11]=clip_coef [12]=max_norm (gradient clipping, below)
-// (The step counter keeps its own one-thread launch: an in-kernel "last workgroup advances it" variant needs one
-//  same-address arrival atomic per workgroup, ~12 ns each and serialised -- 4096 workgroups made the update 55 us.)
-__global__ void adamw_tick_kernel(float* hp) {
-  const float step = hp[5] + 1.0f;
-  hp[5] = step;
-  hp[6] = 1.0f - powf(hp[1], step);
-  hp[7] = 1.0f - powf(hp[2], step);
-}
-// GS: the hp slot of the gradient scale -- 8 (grad_scale) or 9 (grad_scale * clip coefficient, grad_clip_finalize_kernel)
-template <int GS>
-__global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                             bf16* __restrict__ shadow, const float* __restrict__ hp, long long n, int zero_grad) {
-  const float lr = hp[0], b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4], bc1 = hp[6], bc2 = hp[7], gs = hp[GS];
-  const float inv_sqrt_bc2 = 1.0f / sqrtf(bc2), step_size = lr / bc1;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const float gi = g[i] * gs;
-    float pi = p[i] * (1.0f - lr * wd);
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    pi -= step_size * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-    if (shadow) shadow[i] = (bf16)pi;
-    if (zero_grad) g[i] = 0.f;
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// Gradient clipping by global norm (torch.nn.utils.clip_grad_norm_, norm_type 2) on the flat gradient, between the
-// backward and adamw_kernel<9>:  total_norm = hp[8] * sqrt(sum g^2), coef = min(1, hp[12] / (total_norm + 1e-6)),
-// hp[9] = hp[8] * coef.  Two launches, no atomics: the sum has ONE order, fixed by n and the alignment of g alone.
-// The grid depends on n only (never on the CU count), so two boxes add in the same order.
-static inline int grad_clip_blocks(long long n) { return (int)min((n + 4095) / 4096, (long long)1024); }
-
-// partial[b] = sum of g[i]^2 over workgroup b's share.  The 16-byte aligned body is read as float4, vector
-// i -> thread i % (256 * gridDim.x), every thread keeping one running sum per float4 component (fma, in index order);
-// the <= 3 floats in front of the body and the <= 3 behind it go to threads 0.. and 64.. of workgroup 0.  Then
-// (c0 + c1) + (c2 + c3), a 6-step xor butterfly over the wave, (w0 + w1) + (w2 + w3) through LDS.
-// Longest chain of roundings: ceil(nvec / (256 * gridDim.x)) + 1 (head / tail) + 2 + 6 + 2.
-__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const float* __restrict__ g, long long n,
-                                                          float* __restrict__ partial) {
-  const long long head = min(n, (long long)((4 - (int)(((unsigned long long)g >> 2) & 3)) & 3));
-  const float4* __restrict__ body = reinterpret_cast<const float4*>(g + head);
-  const long long nvec = (n - head) >> 2;
-  const long long stride = (long long)gridDim.x * 256;
-  float c0 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f;
-#define VITPE_SQ_ACC(q) do { c0 = fmaf(q.x, q.x, c0); c1 = fmaf(q.y, q.y, c1); c2 = fmaf(q.z, q.z, c2); c3 = fmaf(q.w, q.w, c3); } while (0)
-  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  for (; i + 3 * stride < nvec; i += 4 * stride) {   // four independent 16-B loads in flight, added in index order
-    const float4 q0 = body[i], q1 = body[i + stride], q2 = body[i + 2 * stride], q3 = body[i + 3 * stride];
-    VITPE_SQ_ACC(q0); VITPE_SQ_ACC(q1); VITPE_SQ_ACC(q2); VITPE_SQ_ACC(q3);
-  }
-  for (; i < nvec; i += stride) {
-    const float4 q = body[i];
-    VITPE_SQ_ACC(q);
-  }
-#undef VITPE_SQ_ACC
-  if (blockIdx.x == 0) {
-    const long long tail0 = head + 4 * nvec;
-    const int t = threadIdx.x;
-    if (t < head) c0 = fmaf(g[t], g[t], c0);
-    if (t >= 64 && tail0 + (t - 64) < n) c0 = fmaf(g[tail0 + (t - 64)], g[tail0 + (t - 64)], c0);
-  }
-  float s = (c0 + c1) + (c2 + c3);
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-  __shared__ float ws[4];
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
-}
-// One wave: lane l adds partial[l], partial[l + 64], ... in fp64, then a 6-step xor butterfly in fp64; lane 0 writes
-// hp[10] = total_norm (fp64 product and root, rounded once), hp[11] = coef (fp64 on the ROUNDED norm, rounded once),
-// hp[9] = hp[8] * coef as an fp32 product (coef == 1 leaves hp[8]'s bits).  A NaN norm gives a NaN coef: the clamp is a
-// comparison, not fminf.  nb == 0 (an empty gradient): norm 0, coef 1.
-// (A launch of its own for the reason adamw_tick_kernel is one: "the last workgroup finishes" costs one same-address
-//  arrival atomic per workgroup.)
-__global__ __launch_bounds__(64) void grad_clip_finalize_kernel(const float* __restrict__ partial, int nb, float* hp) {
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nb; i += 64) s += (double)partial[i];
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-  if (threadIdx.x == 0) {
-    const float gs = hp[8];
-    const float norm = (float)((double)gs * sqrt(s));
-    double coef = (double)hp[12] / ((double)norm + 1e-6);
-    coef = coef > 1.0 ? 1.0 : coef;
-    const float cf = nb == 0 ? 1.0f : (float)coef;
-    hp[10] = norm;
-    hp[11] = cf;
-    hp[9] = gs * cf;
-  }
-}
 template <typename T>
 __global__ void cast_kernel(const float* __restrict__ src, T* __restrict__ dst, long long n) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
@@ -1040,28 +939,6 @@ extern "C" int vitpe_embed_bwd(int dtype, const void* dtok, float* dcls, float* 
   VITPE_CHECK_LAUNCH();
 }
 
-extern "C" int vitpe_adamw_step(float* p, float* g, float* m, float* v, void* shadow_bf16, float* hp, long long n,
-                                int zero_grad, hipStream_t st) {
-  VITPE_REQUIRE(p && g && m && v && hp && n >= 0);
-  if (!(zero_grad & 2)) hipLaunchKernelGGL(adamw_tick_kernel, dim3(1), dim3(1), 0, st, hp);   // bit 1: the caller ticked already
-  if (n > 0) {
-    const unsigned blocks = (unsigned)min((n + 255) / 256, (long long)4096);
-    if (zero_grad & 4)   // bit 2: the gradient scale is hp[9] (vitpe_grad_clip wrote it)
-      hipLaunchKernelGGL(adamw_kernel<9>, dim3(blocks), dim3(256), 0, st, p, g, m, v, (bf16*)shadow_bf16, hp, n, zero_grad & 1);
-    else
-      hipLaunchKernelGGL(adamw_kernel<8>, dim3(blocks), dim3(256), 0, st, p, g, m, v, (bf16*)shadow_bf16, hp, n, zero_grad & 1);
-  }
-  VITPE_CHECK_LAUNCH();
-}
-extern "C" int vitpe_grad_clip_blocks(long long n) { return n > 0 ? grad_clip_blocks(n) : 0; }
-extern "C" int vitpe_grad_clip(const float* g, long long n, float* hp, float* partial, int n_partial, hipStream_t st) {
-  VITPE_REQUIRE(hp && n >= 0 && (n == 0 || (g && partial)) && ((unsigned long long)g & 3) == 0);
-  const int nb = n > 0 ? grad_clip_blocks(n) : 0;
-  VITPE_REQUIRE(n_partial >= nb);
-  if (nb > 0) hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(nb), dim3(256), 0, st, g, n, partial);
-  hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(64), 0, st, (const float*)partial, nb, hp);
-  VITPE_CHECK_LAUNCH();
-}
 extern "C" int vitpe_cast(int dtype, const float* src, void* dst, long long n, hipStream_t st) {
   VITPE_REQUIRE(src && dst && n >= 0 && (dtype == 0 || dtype == 1));
   if (n == 0) return 0;

@@ -8,6 +8,8 @@ Layout:
                drop-in mirrors of the reference's models/ package (same class names,
                constructor arguments, attribute and state_dict surface)
   engine.py    the train-step engine: flat parameter/gradient buffers, captured HIP graph,
-               fused AdamW, RCCL gradient all-reduce (replaces train.py:94-125)
+               RCCL gradient all-reduce (replaces train.py:94-125)
+  optim.py     the optimizer side of the step: AdamW state and hp block, gradient clipping, weight EMA,
+               parameter groups, LR schedule (StepOptimizer), and the parameter-group builders
 """
 __version__ = "0.1.0"

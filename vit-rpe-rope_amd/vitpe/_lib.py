@@ -22,6 +22,11 @@ DEBUG_HEADER_PATH = os.path.join(REPO_ROOT, "include", "vitpe_debug.h")   # self
 F32, BF16 = 0, 1
 PE_CODES = {"none": 0, "absolute": 1, "relative": 2, "polynomial": 3, "rope-axial": 4, "rope-mixed": 5}
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_PATCH, EPI_GELU_BWD = range(5)
+# slots of the optimizer's two device blocks (include/vitpe.h: enum vitpe_hp_slot, enum vitpe_sched_slot)
+(HP_LR, HP_BETA1, HP_BETA2, HP_EPS, HP_WEIGHT_DECAY, HP_STEP, HP_BC1, HP_BC2, HP_GRAD_SCALE, HP_CLIP_SCALE, HP_TOTAL_NORM,
+ HP_CLIP_COEF, HP_MAX_NORM, HP_EMA_DECAY, HP_EMA_ORIGIN, HP_EMA_DT, HP_COUNT) = range(17)
+(SCHED_BASE_LR, SCHED_MIN_LR, SCHED_WARMUP, SCHED_TOTAL, SCHED_START_FACTOR, SCHED_ORIGIN, SCHED_LAST_LR, SCHED_SPARE,
+ SCHED_COUNT) = range(9)
 
 
 class VitpeError(RuntimeError):

@@ -30,6 +30,7 @@ from . import ddp
 from . import kernels as K
 from .positional_encoding import (AbsolutePositionalEncoding, PolynomialRPE, RelativePositionalEncoding, RoPEAxial,
                                   RoPEMixed)
+from .optim import StepOptimizer
 from .route import (ALIGN, KIND_FRAG, KIND_FRAG_PHI, KIND_QKV, KIND_QKV_WIDE, KIND_T, Route, resolve_route,  # noqa: F401
                     shadow_plan)
 from .vit import VisionTransformer
@@ -77,71 +78,7 @@ def engine_unsupported(model):
     return sorted(set(active))
 
 
-def vit_layer_id(name: str, depth: int) -> int:
-    """Layer index of parameter `name` for layer-wise learning-rate decay (timm's rule): 0 for the patch embedding, the
-    class token and the position parameters, i + 1 for blocks.i.*, depth + 1 for the final norm and the head."""
-    if name.startswith("blocks."):
-        return int(name.split(".")[1]) + 1
-    if name == "cls_token" or name.startswith(("patch_embed.", "pos_embed.")):
-        return 0
-    return depth + 1
-
-
-def vit_param_groups(model, no_decay: bool = True, layer_decay: Optional[float] = None):
-    """The AdamW parameter groups ViT recipes use, as TrainEngine.set_param_groups takes them (pure host code: works on a
-    CPU model).  no_decay: weight_decay_scale 0 for parameters with ndim <= 1 (LayerNorm gains, biases), cls_token and
-    everything under pos_embed. (the absolute table, the relative bias table, the polynomial coefficients, the
-    rope-mixed freqs).  layer_decay = d: lr_scale = d ** (depth + 1 - vit_layer_id(name)).  Every parameter is in exactly
-    one group; a group also carries its "names" and, with layer_decay, its "layer_id" (set_param_groups ignores both)."""
-    if layer_decay is not None and not (math.isfinite(float(layer_decay)) and float(layer_decay) > 0.0):
-        raise L.VitpeError(f"vit_param_groups: layer_decay must be None or a finite number > 0, got {layer_decay!r}")
-    depth = len(model.blocks)
-    groups: Dict[tuple, dict] = {}
-    for name, prm in model.named_parameters():
-        skip = no_decay and (prm.ndim <= 1 or name == "cls_token" or name.startswith("pos_embed."))
-        lid = vit_layer_id(name, depth) if layer_decay is not None else None
-        key = (lid, skip)
-        if key not in groups:
-            groups[key] = {"params": [], "names": [], "layer_id": lid,
-                           "lr_scale": 1.0 if lid is None else float(layer_decay) ** (depth + 1 - lid),
-                           "weight_decay_scale": 0.0 if skip else 1.0}
-        groups[key]["params"].append(prm)
-        groups[key]["names"].append(name)
-    return list(groups.values())
-
-
-def torch_param_groups(groups, lr: float, weight_decay: float):
-    """`groups` (vit_param_groups / set_param_groups format) as torch.optim.AdamW's param groups: the module path's
-    equivalent of set_param_groups on an engine built with the same lr and weight_decay."""
-    return [{"params": list(g["params"]), "lr": lr * float(g.get("lr_scale", 1.0)),
-             "weight_decay": weight_decay * float(g.get("weight_decay_scale", 1.0))} for g in groups]
-
-
-def param_granule_map(spans, n_flat: int):
-    """uint8 [n_flat / ALIGN]: the group of every ALIGN-element granule of the flat buffers.  spans: (offset, numel, group)
-    per parameter (offsets are multiples of ALIGN, so no granule spans two parameters: a parameter's last granule is its
-    group's together with the zero padding in it, which every group leaves zero); a granule no parameter covers is group 0."""
-    assert n_flat % ALIGN == 0
-    gid = np.zeros(n_flat // ALIGN, dtype=np.uint8)
-    for off, numel, k in spans:
-        assert off % ALIGN == 0 and 0 <= k < 256
-        gid[off // ALIGN:(off + numel + ALIGN - 1) // ALIGN] = k
-    return gid
-
-
 class TrainEngine:
-    # defaults of the two attributes set_grad_clip() / grad_norm() read, so that they answer on an object that never ran
-    # __init__ (tests/test_grad_clip_cpu.py checks their argument handling without a device); __init__ sets both
-    clip_max_norm = _clip_partial = None
-    # likewise what set_ema() reads (tests/test_ema_cpu.py): the decay (None = off), the average's flat buffer, the warm-up
-    # switch, and whether ema_weights() currently has the average swapped into flat_p
-    ema_decay = flat_e = None
-    ema_warmup = _ema_swapped = False
-    # and set_param_groups() / set_lr_schedule() / set_lr() (tests/test_optim_groups_cpu.py): the normalised group list
-    # (None = one group, vitpe_adamw_step), its device map and scale table; the schedule's host copy (None = off) and block
-    param_groups = _gid = _gid_host = _gtab = None
-    lr_sched = _sched = None
-
     def __init__(self, model: VisionTransformer, batch_size: int, compute_dtype=torch.bfloat16, lr=1e-3,
                  weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, process_group=None, use_graph=True, fuse_ln=None,
                  extras=False):
@@ -176,11 +113,6 @@ class TrainEngine:
         self._save_hidden = True
         self._ticked = False                               # _loss(tick=True) on the fused head advanced the step counter
         self._eval_ctl = self._eval_ctl_key = None         # eval_loss's scalars, per distinct batch shape
-        self.clip_max_norm = self._clip_partial = None     # set_grad_clip(): None = clipping off; the clip's work buffer
-        self.ema_decay = self.flat_e = None                # set_ema(): None = no average kept
-        self.ema_warmup = self._ema_swapped = False
-        self.param_groups = self._gid = self._gid_host = self._gtab = None   # set_param_groups(): None = one group
-        self.lr_sched = self._sched = None                 # set_lr_schedule(): None = hp[0] moves only by set_lr()
         self._build_flat(lr, weight_decay, betas, eps)
         self._build_buffers()
         self._build_rng_table()
@@ -221,7 +153,6 @@ class TrainEngine:
         self.n_flat = n
         f = dict(dtype=torch.float32, device=self.dev)
         self.flat_p, self.flat_g = torch.zeros(n, **f), torch.zeros(n, **f)
-        self.flat_m, self.flat_v = torch.zeros(n, **f), torch.zeros(n, **f)
         self.flat_s = torch.zeros(n, dtype=torch.bfloat16, device=self.dev) if self.T == torch.bfloat16 else None
         self._off = offs
         for prm in params:
@@ -231,9 +162,11 @@ class TrainEngine:
             prm.data = view
             prm.grad = self.flat_g[o:o + prm.numel()].view(prm.shape)
         self.model.register_load_state_dict_post_hook(lambda _m, _keys: self.sync_from_model())
-        self.hp = torch.zeros(16, **f)
-        self.hp[:5] = torch.tensor([lr, betas[0], betas[1], eps, wd], **f)
-        self.hp[8] = 1.0 / self.world
+        # everything between the backward and the next forward: optim.StepOptimizer (the moments, the hp block, clip, EMA,
+        # parameter groups, schedule); hp, flat_m and flat_v stay reachable here under their old names
+        self.opt = StepOptimizer(self.flat_p, self.flat_g, self.flat_s, lr, wd, betas, eps, self.world, offs, n,
+                                 self._drop_graphs)
+        self.hp, self.flat_m, self.flat_v = self.opt.hp, self.opt.flat_m, self.opt.flat_v
         # transposed shadows of the GEMM weights (data-gradient GEMMs) and fragment-major packed copies (attention and
         # block-tail kernels): one flat buffer laid out by route.shadow_plan, refreshed by ONE batched kernel per step
         blocks = [(b.attn.qkv.weight, b.attn.proj.weight, b.mlp.fc1.weight, b.mlp.fc2.weight) for b in self.model.blocks]
@@ -334,200 +267,41 @@ class TrainEngine:
             K.cast(self.flat_p, torch.bfloat16, out=self.flat_s)
         K.refresh_shadows(self.flat_p, self._shadow_flat, self._desc, self._ndesc, self._ntiles, self._tile_map)
 
+    # ---------------------------------------------------------------- optimizer side: optim.StepOptimizer does the work
     def set_lr(self, lr: float):
-        if self.lr_sched is not None:
-            raise L.VitpeError("set_lr: a per-step schedule is on and writes hp[0] every step (set_lr_schedule(None) first, "
-                               "or give the schedule its new base_lr)")
-        self.hp[0] = lr
+        self.opt.set_lr(lr)
 
     def current_lr(self) -> float:
-        """hp[0], the learning rate of the last step (the base rate every group scales); synchronises with the device."""
-        return float(self.hp[0].item())
-
-    # ---------------------------------------------------------------- AdamW parameter groups / LR schedule
-    @staticmethod
-    def _group_scales(groups):
-        """set_param_groups' argument, checked as far as host logic goes: [(params, lr_scale, weight_decay_scale)], or None
-        for None / [].  VitpeError for a malformed group, a scale that is not finite and >= 0, a parameter listed twice or
-        more than 255 groups (the map is one byte per granule; group 0 is the unlisted parameters')."""
-        if groups is None or len(groups) == 0:
-            return None
-        out, seen = [], set()
-        for grp in groups:
-            if not isinstance(grp, dict) or "params" not in grp:
-                raise L.VitpeError("set_param_groups: every group is a dict with a 'params' list")
-            scales = []
-            for key in ("lr_scale", "weight_decay_scale"):
-                try:
-                    value = float(grp.get(key, 1.0))
-                except (TypeError, ValueError):
-                    value = float("nan")
-                if not math.isfinite(value) or value < 0.0:
-                    raise L.VitpeError(f"set_param_groups: {key} must be a finite number >= 0, got {grp.get(key)!r}")
-                scales.append(value)
-            params = list(grp["params"])
-            for prm in params:
-                if id(prm) in seen:
-                    raise L.VitpeError("set_param_groups: a parameter is listed twice")
-                seen.add(id(prm))
-            out.append((params, scales[0], scales[1]))
-        if len(out) > 255:
-            raise L.VitpeError(f"set_param_groups: at most 255 groups, got {len(out)}")
-        return out
+        """The learning rate of the last step; synchronises with the device."""
+        return self.opt.current_lr()
 
     def set_param_groups(self, groups):
-        """AdamW parameter groups inside the step ("Parameter groups and LR schedule"): `groups` is a list of
-        {"params": [...], "lr_scale": float, "weight_decay_scale": float} (both scales default to 1, finite and >= 0); the
-        parameters of a group train at lr * lr_scale with weight decay weight_decay * weight_decay_scale, parameters not
-        listed at (1, 1).  vit_param_groups(model, ...) builds the usual list.  None or [] switches the groups off (the
-        default: vitpe_adamw_step, one group).  Scales, not values: set_lr, set_lr_schedule and the engine's weight_decay
-        keep working.  Configuration like max_norm: not part of state_dict().  Switching on or off, or another partition of
-        the parameters, drops the captured graphs; the same partition with new scales is one device write and keeps them.
-        A parameter listed twice or not the model's raises VitpeError.  Every rank must make the same call."""
-        new = self._group_scales(groups)
-        if new is None:
-            if self.param_groups is not None:
-                self._drop_graphs()
-            self.param_groups = self._gid = self._gid_host = self._gtab = None
-            return
-        spans, table = [], [(1.0, 1.0)]
-        for k, (params, lr_scale, wd_scale) in enumerate(new, start=1):
-            table.append((lr_scale, wd_scale))
-            for prm in params:
-                if id(prm) not in self._off:
-                    raise L.VitpeError("set_param_groups: a listed parameter is not one of the model's")
-                spans.append((self._off[id(prm)], prm.numel(), k))
-        gid = param_granule_map(spans, self.n_flat)
-        gtab = torch.tensor(table, dtype=torch.float32)
-        if self._gid_host is not None and self._gtab.shape == gtab.shape and np.array_equal(gid, self._gid_host):
-            self._gtab.copy_(gtab)   # the captured launches read the same two buffers
-        else:
-            self._gid_host, self._gid, self._gtab = gid, torch.from_numpy(gid).to(self.dev), gtab.to(self.dev)
-            self._drop_graphs()
-        self.param_groups = new
-
-    @staticmethod
-    def _sched_values(base_lr, total_steps, warmup_steps, min_lr, warmup_factor, done):
-        """set_lr_schedule's arguments as (base, min, W, T, s0, done), or None for base_lr None; VitpeError unless
-        T > W >= 0, 0 < s0 <= 1, 0 <= min_lr <= base_lr, done >= 0, all finite (T and done below 2^24: fp32 counters)."""
-        if base_lr is None:
-            return None
-        try:
-            base, lo, s0 = float(base_lr), float(min_lr), float(warmup_factor)
-            T, W, dn = int(total_steps), int(warmup_steps), int(done)
-            whole = (T == total_steps and W == warmup_steps and dn == done)
-        except (TypeError, ValueError, OverflowError):
-            base, whole = float("nan"), False
-        if not (whole and all(math.isfinite(x) for x in (base, lo, s0)) and 0.0 <= lo <= base and 0.0 < s0 <= 1.0
-                and 0 <= W < T < 2 ** 24 and 0 <= dn < 2 ** 24):
-            raise L.VitpeError(f"set_lr_schedule: needs total_steps > warmup_steps >= 0, 0 < warmup_factor <= 1, "
-                               f"0 <= min_lr <= base_lr and done >= 0, got base_lr={base_lr!r} total_steps={total_steps!r} "
-                               f"warmup_steps={warmup_steps!r} min_lr={min_lr!r} warmup_factor={warmup_factor!r} done={done!r}")
-        return base, lo, W, T, s0, dn
+        """AdamW parameter groups inside the step: StepOptimizer.set_param_groups."""
+        self.opt.set_param_groups(groups)
 
     def set_lr_schedule(self, base_lr: Optional[float], total_steps: int = 0, warmup_steps: int = 0, min_lr: float = 0.0,
                         warmup_factor: float = 1e-3, done: int = 0):
-        """Linear warm-up + cosine learning rate, stepped every iteration inside the step ("Parameter groups and
-        LR schedule"): step k = `done`, done + 1, ... of the schedule trains at
-            base_lr * (warmup_factor + (1 - warmup_factor) * k / warmup_steps)                      k < warmup_steps
-            min_lr + (base_lr - min_lr) * cos^2(pi / 2 * (k - warmup_steps) / (total_steps - warmup_steps))   up to total_steps
-        and at min_lr from then on -- torch's SequentialLR(LinearLR, CosineAnnealingLR) stepped once per iteration.  The
-        step counter is the optimizer's own, on the device, so replays of the captured step follow the schedule without a
-        host write.  None as base_lr switches the schedule off (the default; hp[0] keeps its last value).  Switching on or
-        off drops the captured graphs; new values for an enabled schedule (the call re-bases it: the next step is step
-        `done`) are device writes and keep them.  Configuration like max_norm: not part of state_dict() -- `done=` is how a
-        resumed run continues.  While it is on, set_lr() raises VitpeError."""
-        new = self._sched_values(base_lr, total_steps, warmup_steps, min_lr, warmup_factor, done)
-        if new is None:
-            if self.lr_sched is not None:
-                self._drop_graphs()
-            self.lr_sched = self._sched = None
-            return
-        base, lo, W, T, s0, dn = new
-        if self._sched is None:
-            self._sched = torch.zeros(8, dtype=torch.float32, device=self.dev)
-            self._drop_graphs()
-        self._sched[:5] = torch.tensor([base, lo, float(W), float(T), s0], dtype=torch.float32, device=self.dev)
-        self._sched[5:6].copy_(self.hp[5:6])   # origin = hp[5] - done, device to device (no host read of the counter)
-        if dn:
-            self._sched[5:6].sub_(float(dn))
-        self.lr_sched = new
+        """Linear warm-up + cosine learning rate, stepped every iteration inside the step: StepOptimizer.set_lr_schedule."""
+        self.opt.set_lr_schedule(base_lr, total_steps, warmup_steps, min_lr, warmup_factor, done)
 
     def set_grad_clip(self, max_norm: Optional[float]):
-        """torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) between the backward (after every all-reduce) and
-        AdamW, inside the step: the norm of the gradient AdamW uses (flat_g * hp[8], all parameters, L2) is reduced on the
-        device and the update scales the gradient by hp[8] * min(1, max_norm / (norm + 1e-6)) ("Gradient
-        clipping").  None or 0 switches it off (the default).  Configuration like the learning rate: not part of
-        state_dict().  Switching on or off drops the captured graphs; a new value for an enabled clip is one device
-        write (hp[12]) and keeps them.  Negative or non-finite values raise VitpeError."""
-        value = 0.0 if max_norm is None else float(max_norm)
-        if not math.isfinite(value) or value < 0.0:
-            raise L.VitpeError(f"set_grad_clip: max_norm must be None or a finite number >= 0, got {max_norm!r}")
-        new = value if value > 0.0 else None
-        if new is not None:
-            if self._clip_partial is None:
-                self._clip_partial = torch.zeros(K.grad_clip_blocks(self.n_flat), dtype=torch.float32, device=self.dev)
-            self.hp[12] = new
-        if (new is None) != (self.clip_max_norm is None):
-            self._drop_graphs()
-        self.clip_max_norm = new
+        """clip_grad_norm_(model.parameters(), max_norm) inside the step: StepOptimizer.set_grad_clip."""
+        self.opt.set_grad_clip(max_norm)
 
-    # ---------------------------------------------------------------- weight EMA
-    @staticmethod
-    def _ema_value(decay) -> Optional[float]:
-        """set_ema's decay argument as the engine keeps it: None for None / 0 (off), the float for 0 < decay < 1;
-        VitpeError for anything else."""
-        value = 0.0 if decay is None else float(decay)
-        if not (math.isfinite(value) and 0.0 <= value < 1.0):
-            raise L.VitpeError(f"set_ema: decay must be None, 0 or a number in (0, 1), got {decay!r}")
-        return value if value > 0.0 else None
-
-    def _ema_guard(self, what):
-        if self._ema_swapped:
-            raise L.VitpeError(f"{what}: not available inside ema_weights() (the parameters are swapped with their average; "
-                               f"leave the context first)")
-
-    def _ema_needs_on(self, what):
-        if self.ema_decay is None:
-            raise L.VitpeError(f"{what}: the weight EMA is off (set_ema(decay) first)")
+    def grad_norm(self) -> float:
+        """total_norm of the last optimizer step, before clipping; synchronises with the device."""
+        return self.opt.grad_norm()
 
     def set_ema(self, decay: Optional[float], warmup: bool = False):
-        """Keep an exponential moving average of the parameters, updated inside the step right after AdamW (DESIGN.md,
-        "Weight EMA"): flat_e += (1 - d_t) * (flat_p - flat_e), with d_t = decay, or with warmup=True
-        min(decay, (1 + t) / (10 + t)) at t = optimizer steps since the average was switched on (TF's num_updates rule).
-        None or 0 switches it off (the default) and frees the buffer.  Switching on allocates flat_e (4 * n_flat bytes),
-        starts it as a copy of the parameters and drops the captured graphs, as do switching off and changing `warmup`; a
-        new decay for an enabled average is one device write (hp[13]) and keeps them.  Configuration-adjacent state like
-        rng_table: not part of model.state_dict() -- ema_state_dict() / load_ema_state_dict() carry it.  Evaluate on the
-        average inside ema_weights().  Values outside [0, 1) raise VitpeError."""
-        self._ema_guard("set_ema")
-        new = self._ema_value(decay)
-        warmup = bool(warmup) and new is not None
-        if new is not None:
-            self.hp[13] = new
-            if self.ema_decay is None:
-                self.flat_e = torch.empty_like(self.flat_p)
-                self._ema_rebase()
-        else:
-            self.flat_e = None
-        if (new is None) != (self.ema_decay is None) or warmup != self.ema_warmup:
-            self._drop_graphs()
-        self.ema_decay, self.ema_warmup = new, warmup
-
-    def _ema_rebase(self):
-        """The average starts over from the parameters, its warm-up from now: hp[14] = hp[5], device to device."""
-        self.flat_e.copy_(self.flat_p)
-        self.hp[14:15].copy_(self.hp[5:6])
+        """Keep an exponential moving average of the parameters, updated inside the step: StepOptimizer.set_ema."""
+        self.opt.set_ema(decay, warmup)
 
     def reset_ema(self):
-        """Restart the average as a copy of the current parameters (after loading or broadcasting parameters); captured
-        graphs stay valid."""
-        self._ema_guard("reset_ema")
-        self._ema_needs_on("reset_ema")
-        self._ema_rebase()
+        """Restart the average as a copy of the current parameters; captured graphs stay valid."""
+        self.opt.reset_ema()
 
     def _ema_swap(self):
-        K.ema_swap(self.flat_p, self.flat_e, self.flat_s)
+        K.ema_swap(self.flat_p, self.opt.flat_e, self.flat_s)
         self.refresh_shadows(cast_flat=False)
 
     @contextlib.contextmanager
@@ -537,15 +311,15 @@ class TrainEngine:
         model.state_dict() all see the averaged weights -- no second set of shadows exists.  Leaving (also by an exception)
         exchanges them back: flat_p, flat_e, flat_s and the shadows return bit for bit, no pointer moves, captured graphs
         stay valid.  Training calls, capture(), set_ema() and a nested ema_weights() raise VitpeError inside."""
-        self._ema_guard("ema_weights")
-        self._ema_needs_on("ema_weights")
+        self.opt.guard("ema_weights")
+        self.opt.needs_ema("ema_weights")
         self._ema_swap()
-        self._ema_swapped = True
+        self.opt.ema_swapped = True
         try:
             yield self
         finally:
             self._ema_swap()
-            self._ema_swapped = False
+            self.opt.ema_swapped = False
 
     def _param_spans(self):
         """(state_dict key, offset into the flat buffers, parameter) of every parameter."""
@@ -554,8 +328,8 @@ class TrainEngine:
     def ema_state_dict(self):
         """model.state_dict() with every parameter entry replaced by a clone of its average (buffers as they are); nothing
         is swapped.  Inside ema_weights() the same values (they sit in flat_p then)."""
-        self._ema_needs_on("ema_state_dict")
-        src = self.flat_p if self._ema_swapped else self.flat_e
+        self.opt.needs_ema("ema_state_dict")
+        src = self.flat_p if self.opt.ema_swapped else self.opt.flat_e
         sd = self.model.state_dict()
         for name, o, prm in self._param_spans():
             sd[name] = src[o:o + prm.numel()].view(prm.shape).clone()
@@ -564,23 +338,14 @@ class TrainEngine:
     def load_ema_state_dict(self, sd):
         """The inverse of ema_state_dict(): the parameter entries of `sd` become the average (other keys are ignored; a
         missing or mis-shaped parameter raises VitpeError).  The parameters themselves are not touched."""
-        self._ema_guard("load_ema_state_dict")
-        self._ema_needs_on("load_ema_state_dict")
+        self.opt.guard("load_ema_state_dict")
+        self.opt.needs_ema("load_ema_state_dict")
         spans = self._param_spans()
         for name, _, prm in spans:
             if name not in sd or tuple(sd[name].shape) != tuple(prm.shape):
                 raise L.VitpeError(f"load_ema_state_dict: no entry of shape {tuple(prm.shape)} for parameter {name!r}")
         for name, o, prm in spans:
-            self.flat_e[o:o + prm.numel()].view(prm.shape).copy_(sd[name])
-
-    def grad_norm(self) -> float:
-        """total_norm of the last optimizer step, before clipping (what clip_grad_norm_ returns), read from hp[10];
-        synchronises with the device.  Only defined while clipping is on (nothing computes the norm otherwise):
-        VitpeError when it is off."""
-        if self.clip_max_norm is None:
-            raise L.VitpeError("grad_norm: gradient clipping is off (set_grad_clip(max_norm) first); the norm is only "
-                               "computed as part of the clip")
-        return float(self.hp[10].item())
+            self.opt.flat_e[o:o + prm.numel()].view(prm.shape).copy_(sd[name])
 
     # ---------------------------------------------------------------- activations
     def _build_buffers(self):
@@ -1015,20 +780,8 @@ class TrainEngine:
             self._wgrad_group(part)
 
     def _optimizer(self):
-        clip = self.clip_max_norm is not None
-        if self.lr_sched is not None:   # hp[0] of this step, before anything reads it
-            K.lr_schedule(self.hp, self._sched, ticked=self._ticked)
-        if clip:   # after every all-reduce in every step shape: all ranks reduce the same flat_g to the same coefficient
-            K.grad_clip(self.flat_g, self.hp, self._clip_partial)
-        if self.param_groups is None:
-            K.adamw_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.hp, shadow_bf16=self.flat_s,
-                         ticked=self._ticked, zero_grad=True, clipped=clip)
-        else:
-            K.adamw_step_groups(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.hp, self._gid, self._gtab,
-                                shadow_bf16=self.flat_s, ticked=self._ticked, zero_grad=True, clipped=clip)
+        self.opt.launch(self._ticked)
         self._ticked = False
-        if self.ema_decay is not None:   # on the updated parameters; hp[5] already counts this step
-            K.ema_update(self.flat_p, self.flat_e, self.hp, self.ema_warmup)
         self.refresh_shadows(cast_flat=False)
         if self.extras:   # the step's last launch, after the backward has regenerated the forward's masks: the next step
             K.rng_advance(self.rng_table, 1)   # (or replay) draws new ones.  Once per step in every step shape
@@ -1065,17 +818,16 @@ class TrainEngine:
         if self.world > 1:
             ddp.broadcast_(self.flat_p, src, self.pg)
             self.refresh_shadows()
-        if self.ema_decay is not None:   # the average of parameters that have just been replaced means nothing
+        if self.opt.ema_decay is not None:   # the average of parameters that have just been replaced means nothing
             self.reset_ema()
 
     def capture(self):
         """Warm up on a side stream, then capture forward+loss+backward (and, single-GPU, the
         optimizer) into HIP graphs.  Engine state is restored after the warm-up."""
-        self._ema_guard("capture")
-        state = (self.flat_p, self.flat_m, self.flat_v, self.hp, self.metric_acc) + ((self.rng_table,) if self.extras else ())
-        state += (self.flat_e,) if self.ema_decay is not None else ()   # (the warm-up's two steps would move the average)
-        state += (self.aug_rng,) if self.aug_rng is not None else ()
-        state += (self._sched,) if self.lr_sched is not None else ()    # (sched[6]; hp[0] and hp[5] return with hp)
+        self.opt.guard("capture")
+        # everything the two warm-up steps move: the optimizer lists its own (StepOptimizer.state_tensors)
+        state = [self.flat_p, self.metric_acc, *self.opt.state_tensors(),
+                 *(t for t in (self.rng_table, self.aug_rng) if t is not None)]
         snap = [t.clone() for t in state]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -1173,7 +925,7 @@ class TrainEngine:
         batch (n < B; the reference DataLoader has no drop_last, train.py:89-90) runs through the same captured
         graph with the padding masked on the device.  `n_valid_global`: size of the global batch over all ranks
         (default n * world); `n_valid` < n marks trailing indices as padding too (a rank with an empty share)."""
-        self._ema_guard("step_indexed")
+        self.opt.guard("step_indexed")
         n = self._load_indices(idx)
         self.set_valid(n if n_valid is None else min(n, n_valid), n_valid_global)
         self.step()
@@ -1216,7 +968,7 @@ class TrainEngine:
         n <= B (a ragged last batch is padded and masked, see set_valid); None re-uses the resident batch.  No host
         synchronisation.  `exchange=False` skips the gradient all-reduce (measurement of the exposed communication
         time only: the replicas diverge)."""
-        self._ema_guard("step")
+        self.opt.guard("step")
         if self.aug_rng is not None and self.dataset is None:   # never train silently without the crop
             raise L.VitpeError(self._AUG_NEEDS_DATASET)
         if images is not None:
@@ -1262,7 +1014,7 @@ class TrainEngine:
 
     def forward_backward(self):
         """forward + loss + backward on the resident batch without the optimizer (tests / parity)."""
-        self._ema_guard("forward_backward")
+        self.opt.guard("forward_backward")
         self._fwd_train(); self._loss(tick=False); self._backward()
 
     def forward_only(self, images: torch.Tensor, labels: Optional[torch.Tensor] = None) -> torch.Tensor:
