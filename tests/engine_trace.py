@@ -11,7 +11,9 @@ The trailing stream argument is dropped.  Nothing in the product code knows abou
 
 CONFIGS are the engine configurations of tests/test_engine_trace_gpu.py and tests/test_engine_route_cpu.py; the golden
 (tests/golden/engine_trace.json) holds per configuration the route flags and per sequence the call names (one string,
-space-separated) and the SHA-256 of the canonical full trace.  Run as a script on the GPU:
+space-separated) and the SHA-256 of the canonical full trace.  The sequences (SEQUENCES) run in order on one engine: `step`,
+`eval`, `parts` always; `probes`, `ema` and `evalloss` (the head's evaluation path: eval_loss and read_metrics) where the
+configuration asks for them.  Run as a script on the GPU:
 
     python tests/engine_trace.py --dump DIR            full traces, one JSON file per configuration and sequence
     python tests/engine_trace.py --write-golden FILE   the golden (only ever from the commit BEFORE an engine refactor)
@@ -49,18 +51,19 @@ BATCH = 2
 
 
 def _cfg(geom="CIFAR", env=None, dtype="bf16", fuse_ln=None, extras=False, model=None, pe="rope-axial", depth=3,
-         dataset=False, probes=False, optim=None):
-    """optim: the optimizer-side options, {"clip": max_norm, "ema": (decay, warmup), "groups": vit_param_groups' keywords,
+         dataset=False, probes=False, evalloss=False, optim=None):
+    """evalloss: also trace the head's evaluation path (the `evalloss` sequence).
+    optim: the optimizer-side options, {"clip": max_norm, "ema": (decay, warmup), "groups": vit_param_groups' keywords,
     "sched": set_lr_schedule's arguments}, each applied through the engine's public method when present."""
     return dict(geom=geom, env=env or {}, dtype=dtype, fuse_ln=fuse_ln, extras=extras, model=model or {}, pe=pe, depth=depth,
-                dataset=dataset, probes=probes, optim=optim or {})
+                dataset=dataset, probes=probes, evalloss=evalloss, optim=optim or {})
 
 
-CONFIGS = {"cifar-bf16": _cfg(probes=True)}
+CONFIGS = {"cifar-bf16": _cfg(probes=True, evalloss=True)}
 CONFIGS["VITPE_RECOMPUTE_LN=1"] = _cfg(env={"VITPE_RECOMPUTE_LN": "1"})
 for _s in ROUTE_SWITCHES:
     if _s not in ("VITPE_FUSE_LN", "VITPE_RECOMPUTE_LN"):
-        CONFIGS[_s + "=0"] = _cfg(env={_s: "0"})
+        CONFIGS[_s + "=0"] = _cfg(env={_s: "0"}, evalloss=(_s == "VITPE_FUSE_HEAD"))   # (the unfused head: head_bwd)
 CONFIGS.update({
     "fuse_ln=fwd": _cfg(fuse_ln="fwd"),
     "fuse_ln=False": _cfg(fuse_ln=False),
@@ -238,7 +241,25 @@ def _seq_ema(eng, images, labels, idx):
         _seq_eval(eng, images, labels, idx)
 
 
-SEQUENCES = (("step", _seq_step), ("eval", _seq_eval), ("parts", _seq_parts), ("probes", _seq_probes), ("ema", _seq_ema))
+def _seq_evalloss(eng, images, labels, idx):
+    """The head's evaluation path: logits, then eval_loss on a full batch twice (one cached control block), on a ragged
+    share of a global batch of 2 (another block), and the metrics read."""
+    eng.forward_only(images, labels)
+    acc = torch.zeros(2, device="cuda")
+    eng.eval_loss(2, acc)
+    eng.eval_loss(2, acc)
+    eng.eval_loss(1, acc, 2)
+    eng.read_metrics()
+
+
+def _check_evalloss(calls):
+    """the control block of cross_entropy_ctl (argument 6 of the call): cached for the repeated shape, new for the other"""
+    ctl = [c[6] for c in calls if c[0] == "cross_entropy_ctl"]
+    assert len(ctl) == 3 and ctl[0] == ctl[1] != ctl[2], ctl
+
+
+SEQUENCES = (("step", _seq_step), ("eval", _seq_eval), ("parts", _seq_parts), ("probes", _seq_probes), ("ema", _seq_ema),
+             ("evalloss", _seq_evalloss))
 
 
 def trace_config(name):
@@ -249,11 +270,14 @@ def trace_config(name):
         route = {f: bool(getattr(eng, f)) for f in ROUTE_FLAGS}
         traces = {}
         for seq, run in SEQUENCES:
-            if (seq == "probes" and not cfg["probes"]) or (seq == "ema" and "ema" not in cfg["optim"]):
+            if ((seq == "probes" and not cfg["probes"]) or (seq == "ema" and "ema" not in cfg["optim"])
+                    or (seq == "evalloss" and not cfg["evalloss"])):
                 continue
             with recording() as calls:
                 run(eng, images, labels, idx)
             torch.cuda.synchronize()
+            if seq == "evalloss":
+                _check_evalloss(calls)
             traces[seq] = calls
     return route, traces
 

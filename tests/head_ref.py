@@ -1,4 +1,4 @@
-"""Float64 restatement of the classifier head and its loss (csrc/misc.hip: head_fwd_kernel, ce_kernel, head_step_kernel,
+"""Float64 restatement of the classifier head and its loss (csrc/head.hip: head_fwd_kernel, ce_kernel, head_step_kernel,
 head_bwd_rows_kernel, head_bwd_params_kernel), the input builders and the case lists.  Shared by
 tests/test_head_loss_cpu.py (the reference against torch.nn.functional autograd and against closed forms; a plain fp32
 restatement inside the gates) and tests/test_head_loss_gpu.py (the kernels against it).  No GPU and no vitpe import here.
@@ -69,7 +69,7 @@ CE_CASES = [(1, 1), (1, 1000), (255, 2), (256, 10), (257, 100), (600, 1000), (60
 
 
 def head_step_instance(D, Cn):
-    """(KD, WLDS) of head_step_kernel that vitpe_head_step launches for this head (csrc/misc.hip: head_step_launch)."""
+    """(KD, WLDS) of head_step_kernel that vitpe_head_step launches for this head (csrc/head.hip: head_step_launch)."""
     kd = (D + 63) // 64
     return (2 if kd <= 2 else 3 if kd == 3 else 6 if kd <= 6 else 12), Cn * D <= 16 * 768
 

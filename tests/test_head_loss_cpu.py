@@ -8,7 +8,8 @@
   * a plain fp32 torch restatement of the same formulas stays inside every gate the GPU test applies (the reference alone
     leaves a correct fp32 implementation inside the gates, per image row as well);
   * the float64 class-row gradient rounded to bf16 satisfies the bf16 dx bound;
-  * the case list launches every reachable instantiation of head_step_kernel in both dtypes.
+  * the case list launches every reachable instantiation of head_step_kernel in both dtypes;
+  * a real vitpe.head.StepHead over CPU tensors: the control block set_valid writes, its defaults, refusals and caching.
 """
 import math
 
@@ -123,3 +124,36 @@ def test_case_list_reaches_every_instantiation():
         (True, False, False, False), (False, False, True, False), (False, False, False, True)}
     ragged_global = {c[0] for c in H.HEAD_STEP_CASES if not H.head_step_instance(c[3], c[4])[1] and 0 < c[5] < c[1]}
     assert ragged_global == {"f32", "bf16"}
+
+
+def test_step_head_set_valid_writes_the_control_block_without_a_device():
+    """StepHead over CPU tensors, world 2, batch 4: set_valid leaves float32 {world / n_global, 1 / n_global, n_valid, 0};
+    the global count defaults to n_valid * world; counts outside the batch raise; an unchanged pair writes nothing."""
+    from vitpe._lib import VitpeError
+    from vitpe.head import StepHead
+    B, N, D, Cn = 4, 3, 8, 5
+    norm, lin = torch.nn.LayerNorm(D), torch.nn.Linear(D, Cn)
+    grads = [torch.zeros_like(p) for p in (lin.weight, lin.bias, norm.weight, norm.bias)]
+    dx = torch.ones(B, N, D)
+    head = StepHead(norm, lin, grads, torch.zeros(B, N, D), dx, torch.zeros(B, dtype=torch.int64), torch.zeros(16),
+                    torch.float32, N, True, world=2)
+    f32 = lambda *v: torch.tensor(v, dtype=torch.float32)  # noqa: E731
+    assert head.ctl.dtype == torch.float32 and head.valid == (B, 2 * B)
+    assert torch.equal(head.ctl, f32(2 / 8, 1 / 8, 4, 0))          # the constructor's set_valid(B)
+    assert not dx.any() and head.ticked is False                  # the zero rows of dx_out[L] are the head's to establish
+    head.set_valid(3, 5)
+    assert torch.equal(head.ctl, f32(2 / 5, 1 / 5, 3, 0))
+    head.set_valid(3)
+    assert head.valid == (3, 6) and torch.equal(head.ctl, f32(2 / 6, 1 / 6, 3, 0))
+    head.set_valid(0, 1)                                           # a rank with an empty share of a global batch of 1
+    assert torch.equal(head.ctl, f32(2.0, 1.0, 0, 0))
+    for bad in ((B + 1, None), (-1, None), (-1, 4), (3, 2), (0, 0)):
+        with pytest.raises(VitpeError):
+            head.set_valid(*bad)
+    assert head.valid == (0, 1) and torch.equal(head.ctl, f32(2.0, 1.0, 0, 0))   # a refused call changes nothing
+    head.set_valid(3, 5)
+    head.ctl.fill_(7.0)
+    head.set_valid(3, 5)                                           # the pair it was last set for: no write
+    assert torch.equal(head.ctl, torch.full((4,), 7.0))
+    head.set_valid(3, 6)
+    assert torch.equal(head.ctl, f32(2 / 6, 1 / 6, 3, 0))

@@ -1,4 +1,4 @@
-"""The classifier head, the loss and embed_bwd (csrc/misc.hip) through the C ABI against the float64 reference of
+"""The classifier head, the loss and embed_bwd (csrc/head.hip, csrc/embed.hip) through the C ABI against the float64 reference of
 tests/head_ref.py, at the shapes where the kernels take another path:
 
   vitpe_head_step          every (KD, WLDS) instantiation a valid (D <= 768, Cn <= 64) reaches, in both dtypes (case list and

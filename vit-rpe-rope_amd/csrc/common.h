@@ -314,7 +314,7 @@ enum { SCHED_BASE_LR = 0, SCHED_MIN_LR = 1, SCHED_WARMUP = 2, SCHED_TOTAL = 3, S
        SCHED_LAST_LR = 6, SCHED_SPARE = 7, SCHED_COUNT = 8 };
 
 // The optimizer's step counter and bias corrections, one lane: adamw_tick_kernel (optim.hip) and the hp_tick branch of the
-// head's backward (misc.hip) both run this.
+// head's backward (head.hip) both run this.
 VITPE_DEV void adamw_tick(float* hp) {
   const float step = hp[HP_STEP] + 1.0f;
   hp[HP_STEP] = step;

@@ -221,6 +221,132 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(EmbedArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// The un-fused route (geometries outside vitpe_patch_embed_supported, VITPE_FUSE_EMBED=0) and the embedding's backward:
+// the unfold as a launch of its own in front of the patch GEMM, from fp32 images or from the resident uint8 dataset
+// (with the same augmentation stream), and embed_bwd.
+// Patch-embed unfold (reference models/vit.py:164,248-250: Conv2d(k=s=p) == unfold + GEMM).
+// patches[(b*P + gy*g + gx)][c*p*p + ky*p + kx] = img[b][c][gy*p+ky][gx*p+kx]
+// One thread per (b, patch, c, ky) moves p contiguous pixels (fp32 in, T out).
+template <typename T>
+__global__ void unfold_kernel(const float* __restrict__ img, T* __restrict__ patches, int B, int Cc, int S, int p) {
+  const int g = S / p, P = g * g, Kp = Cc * p * p;
+  const long long total = (long long)B * P * Cc * p;
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+       idx += (long long)gridDim.x * blockDim.x) {
+    const int ky = (int)(idx % p);
+    long long t = idx / p;
+    const int ch = (int)(t % Cc); t /= Cc;
+    const int n = (int)(t % P);
+    const int b = (int)(t / P);
+    const int gy = n / g, gx = n % g;
+    const float* src = img + (((size_t)b * Cc + ch) * S + gy * p + ky) * S + gx * p;
+    T* dst = patches + ((size_t)b * P + n) * Kp + ch * p * p + ky * p;
+    for (int kx = 0; kx < p; ++kx) dst[kx] = from_f32<T>(src[kx]);
+  }
+}
+
+// bf16, p % 8 == 0 (224 / 16): one thread per 8 pixels -- two 16-B loads, one 16-B store; consecutive threads write
+// consecutive 16-B pieces of the patch matrix (the scalar loop above ran at 0.7 TB/s: 78 us per ViT-B/16 step)
+__global__ void unfold8_kernel(const float* __restrict__ img, bf16* __restrict__ patches, int B, int Cc, int S, int p) {
+  const int g = S / p, P = g * g, Kp = Cc * p * p, p8 = p / 8;
+  const long long total = (long long)B * P * Cc * p * p8;
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+       idx += (long long)gridDim.x * blockDim.x) {
+    const int hx = (int)(idx % p8);
+    long long t = idx / p8;
+    const int ky = (int)(t % p); t /= p;
+    const int ch = (int)(t % Cc); t /= Cc;
+    const int n = (int)(t % P);
+    const int b = (int)(t / P);
+    const int gy = n / g, gx = n % g;
+    const float* src = img + (((size_t)b * Cc + ch) * S + gy * p + ky) * S + gx * p + 8 * hx;
+    const f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 4);
+    float f[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+    *reinterpret_cast<Chunk16*>(patches + ((size_t)b * P + n) * Kp + ch * p * p + ky * p + 8 * hx) = f32_to_chunk<bf16>(f);
+  }
+}
+
+// Same from a uint8 dataset resident in HBM (reference train.py:69-92: DataLoader gather ->
+// ToTensor (x/255) -> Normalize((x-mean)/std) -> model): record index[b] of data [Ndata,C,S,S] (the
+// CIFAR-10 binary / MNIST idx pixel order) is normalised in fp32 with the reference's operation
+// order and written straight as the patch matrix; img_out (nullable) receives the fp32 image.
+// AUG (vitpe_unfold_u8_aug): the source pixel goes through the augmentation stream of augment.h (random crop with zero
+// padding + horizontal flip per batch slot b); the draw is repeated only when a thread moves on to another image.
+template <typename T, bool AUG>
+__global__ void unfold_u8_kernel(const unsigned char* __restrict__ data, const long long* __restrict__ index,
+                                 const float* __restrict__ mean, const float* __restrict__ stdv, T* __restrict__ patches,
+                                 float* __restrict__ img_out, int B, int Cc, int S, int p,
+                                 const unsigned long long* __restrict__ rng, int pad, int hflip) {
+  const int g = S / p, P = g * g, Kp = Cc * p * p;
+  const long long total = (long long)B * P * Cc * p;
+  AugDraw aug = {0, 0, 0};
+  int aug_b = -1;
+  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+       idx += (long long)gridDim.x * blockDim.x) {
+    const int ky = (int)(idx % p);
+    long long t = idx / p;
+    const int ch = (int)(t % Cc); t /= Cc;
+    const int n = (int)(t % P);
+    const int b = (int)(t / P);
+    const int gy = n / g, gx = n % g;
+    const long long rec = index != nullptr ? index[b] : (long long)b;
+    const size_t pix = ((size_t)ch * S + gy * p + ky) * S + gx * p;
+    const unsigned char* src = data + (size_t)rec * Cc * S * S + pix;
+    T* dst = patches + ((size_t)b * P + n) * Kp + ch * p * p + ky * p;
+    const float m = mean[ch], sd = stdv[ch];
+    if (AUG) {
+      if (b != aug_b) { aug = aug_draw(rng, (unsigned long long)b, pad, hflip); aug_b = b; }
+      const int sy = gy * p + ky + aug.oy - pad;
+      const bool rowok = sy >= 0 && sy < S;
+      const unsigned char* row = data + (size_t)rec * Cc * S * S + ((size_t)ch * S + (rowok ? sy : 0)) * S;
+      for (int kx = 0; kx < p; ++kx) {
+        const int sx = (aug.flip ? S - 1 - (gx * p + kx) : gx * p + kx) + aug.ox - pad;
+        unsigned char u = 0;   // the zero padding
+        if (rowok && sx >= 0 && sx < S) u = row[sx];
+        const float v = ((float)u / 255.0f - m) / sd;
+        dst[kx] = from_f32<T>(v);
+        if (img_out != nullptr) img_out[(size_t)b * Cc * S * S + pix + kx] = v;
+      }
+      continue;
+    }
+    for (int kx = 0; kx < p; ++kx) {
+      const float v = ((float)src[kx] / 255.0f - m) / sd;   // ToTensor then Normalize, IEEE division
+      dst[kx] = from_f32<T>(v);
+      if (img_out != nullptr) img_out[(size_t)b * Cc * S * S + pix + kx] = v;
+    }
+  }
+}
+
+// the draws of the first B batch slots as integers (tests): out [B,3] = (oy, ox, flip)
+__global__ void augment_params_kernel(const unsigned long long* __restrict__ rng, int* __restrict__ out, int B, int pad,
+                                      int hflip) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const AugDraw d = aug_draw(rng, (unsigned long long)b, pad, hflip);
+  out[3 * b] = d.oy; out[3 * b + 1] = d.ox; out[3 * b + 2] = d.flip;
+}
+
+// patch-embed parameter gradients that are plain column sums of the token gradient:
+//   dcls[d] += sum_b dtok[b,0,d] ; dape[p][d] += sum_b dtok[b,1+p,d]   (vit.py:253-258)
+// and repacking of the patch-token gradient rows into the GEMM layout [B*P, D]
+template <typename T>
+__global__ void embed_bwd_kernel(const T* __restrict__ dtok, float* dcls, float* dape, T* __restrict__ dpatch,
+                                 int B, int Ntok, int D, int bchunk) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;  // over Ntok*D ; blockIdx.y over batch chunks
+  if (idx >= Ntok * D) return;
+  const int n = idx / D, d = idx % D;
+  const int b0 = blockIdx.y * bchunk, b1 = min(B, b0 + bchunk);
+  float s = 0.f;
+  for (int b = b0; b < b1; ++b) {
+    const T v = dtok[((size_t)b * Ntok + n) * D + d];
+    s += to_f32(v);
+    if (n >= 1) dpatch[((size_t)b * (Ntok - 1) + n - 1) * D + d] = v;
+  }
+  if (n == 0) atomicAdd(dcls + d, s);
+  else if (dape) atomicAdd(dape + (size_t)(n - 1) * D + d, s);
+}
+
 }  // namespace vitpe
 
 using namespace vitpe;
@@ -274,4 +400,74 @@ extern "C" int vitpe_patch_embed_aug(int dtype, const float* img, const unsigned
                                      int pad, int hflip, hipStream_t stream) {
   return launch_patch_embed(dtype, img, data, index, nmean, nstd, W, bias, cls, ape, tokens, patches, mean, rstd, B, C, S, p, D,
                             eps, rng, pad, hflip, stream);
+}
+
+extern "C" int vitpe_unfold(int dtype, const float* img, void* patches, int B, int C, int S, int p, hipStream_t st) {
+  VITPE_REQUIRE(img && patches && B >= 0 && C > 0 && p > 0 && S % p == 0 && (dtype == 0 || dtype == 1));
+  const long long total = (long long)B * (S / p) * (S / p) * C * p;
+  if (total == 0) return 0;
+  const unsigned blocks = (unsigned)min((total + 255) / 256, (long long)8192);
+  if (dtype == 1 && p % 8 == 0) {   // (image rows are S fp32 = a multiple of 32 B, patch rows p^2 bf16: every piece is 16-B aligned)
+    const long long total8 = total * (p / 8);
+    hipLaunchKernelGGL(unfold8_kernel, dim3((unsigned)min((total8 + 255) / 256, (long long)16384)), dim3(256), 0, st, img,
+                       (bf16*)patches, B, C, S, p);
+    VITPE_CHECK_LAUNCH();
+  }
+  if (dtype == 1) hipLaunchKernelGGL(unfold_kernel<bf16>, dim3(blocks), dim3(256), 0, st, img, (bf16*)patches, B, C, S, p);
+  else hipLaunchKernelGGL(unfold_kernel<float>, dim3(blocks), dim3(256), 0, st, img, (float*)patches, B, C, S, p);
+  VITPE_CHECK_LAUNCH();
+}
+
+static int launch_unfold_u8(int dtype, const unsigned char* data, const long long* index, const float* mean,
+                            const float* stdv, void* patches, float* img_out, int B, int C, int S, int p,
+                            const unsigned long long* rng, int pad, int hflip, hipStream_t st) {
+  VITPE_REQUIRE(data && mean && stdv && patches && B >= 0 && C > 0 && p > 0 && S % p == 0 && (dtype == 0 || dtype == 1));
+  VITPE_REQUIRE(rng == nullptr || (pad >= 0 && pad <= S));
+  const long long total = (long long)B * (S / p) * (S / p) * C * p;
+  if (total == 0) return 0;
+  const unsigned blocks = (unsigned)min((total + 255) / 256, (long long)8192);
+  if (rng != nullptr) {
+    if (dtype == 1)
+      hipLaunchKernelGGL((unfold_u8_kernel<bf16, true>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (bf16*)patches, img_out, B, C, S, p, rng, pad, hflip);
+    else
+      hipLaunchKernelGGL((unfold_u8_kernel<float, true>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (float*)patches, img_out, B, C, S, p, rng, pad, hflip);
+  } else {
+    if (dtype == 1)
+      hipLaunchKernelGGL((unfold_u8_kernel<bf16, false>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (bf16*)patches, img_out, B, C, S, p, rng, 0, 0);
+    else
+      hipLaunchKernelGGL((unfold_u8_kernel<float, false>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (float*)patches, img_out, B, C, S, p, rng, 0, 0);
+  }
+  VITPE_CHECK_LAUNCH();
+}
+
+extern "C" int vitpe_unfold_u8(int dtype, const unsigned char* data, const long long* index, const float* mean,
+                               const float* stdv, void* patches, float* img_out, int B, int C, int S, int p,
+                               hipStream_t st) {
+  return launch_unfold_u8(dtype, data, index, mean, stdv, patches, img_out, B, C, S, p, nullptr, 0, 0, st);
+}
+
+// the same with the augmentation stream (rng NULL: exactly vitpe_unfold_u8)
+extern "C" int vitpe_unfold_u8_aug(int dtype, const unsigned char* data, const long long* index, const float* mean,
+                                   const float* stdv, void* patches, float* img_out, int B, int C, int S, int p,
+                                   const unsigned long long* rng, int pad, int hflip, hipStream_t st) {
+  return launch_unfold_u8(dtype, data, index, mean, stdv, patches, img_out, B, C, S, p, rng, pad, hflip, st);
+}
+
+extern "C" int vitpe_augment_params(const unsigned long long* rng, int* out, int B, int pad, int hflip, hipStream_t st) {
+  VITPE_REQUIRE(rng && B >= 0 && (out || B == 0) && pad >= 0);
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(augment_params_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, rng, out, B, pad, hflip);
+  VITPE_CHECK_LAUNCH();
+}
+
+extern "C" int vitpe_embed_bwd(int dtype, const void* dtok, float* dcls, float* dape, void* dpatch, int B, int Ntok,
+                               int D, hipStream_t st) {
+  VITPE_REQUIRE(dtok && dcls && dpatch && B >= 0 && (dtype == 0 || dtype == 1));
+  if (dtype == 1)
+    hipLaunchKernelGGL(embed_bwd_kernel<bf16>, dim3((Ntok * D + 255) / 256, (B + 15) / 16), dim3(256), 0, st,
+                       (const bf16*)dtok, dcls, dape, (bf16*)dpatch, B, Ntok, D, 16);
+  else
+    hipLaunchKernelGGL(embed_bwd_kernel<float>, dim3((Ntok * D + 255) / 256, (B + 15) / 16), dim3(256), 0, st,
+                       (const float*)dtok, dcls, dape, (float*)dpatch, B, Ntok, D, 16);
+  VITPE_CHECK_LAUNCH();
 }

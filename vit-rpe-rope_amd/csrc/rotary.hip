@@ -8,6 +8,23 @@
 
 namespace vitpe {
 
+// stand-alone rotate-half (models/rope_utils.py:3-37): x [B,H,P,HD] fp32, cos/sin [P,HD/2] or [H,P,HD/2]
+__global__ void rotary_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ cosv,
+                              const float* __restrict__ sinv, long long total_pairs, int H, int P, int half, int per_head) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total_pairs) return;
+  const int f = (int)(idx % half);
+  long long t = idx / half;
+  const int n = (int)(t % P); t /= P;
+  const int h = (int)(t % H);
+  const size_t row = (size_t)(idx / half) * 2 * half;
+  const size_t o = ((per_head ? (size_t)h * P : 0) + n) * half + f;
+  const float c = cosv[o], s = sinv[o];
+  const float x1 = x[row + f], x2 = x[row + half + f];
+  y[row + f] = __fsub_rn(__fmul_rn(x1, c), __fmul_rn(x2, s));
+  y[row + half + f] = __fadd_rn(__fmul_rn(x1, s), __fmul_rn(x2, c));
+}
+
 // one thread per table entry `col` of [L] (L = (per_head ? H : 1) * P * half) and slice blockIdx.y of the R = B (per head)
 // or B * H (shared table) rows of x that use it: dx of those rows, and the slice's partial d cos / d sin
 //   dx1 = g1 c + g2 s ,  dx2 = g2 c - g1 s ,  dcos += g1 x1 + g2 x2 ,  dsin += g2 x1 - g1 x2
@@ -110,6 +127,15 @@ int reduce_parts(float* part, int R, long long L, float* dst0, float* dst1, hipS
 }  // namespace vitpe
 
 using namespace vitpe;
+
+extern "C" int vitpe_apply_rotary(const float* x, float* y, const float* cosv, const float* sinv, int B, int H, int P,
+                                  int HD, int per_head, hipStream_t st) {
+  VITPE_REQUIRE(x && y && cosv && sinv && B >= 0 && H > 0 && P > 0 && HD > 0 && HD % 2 == 0);
+  const long long total = (long long)B * H * P * (HD / 2);
+  if (total == 0) return 0;
+  hipLaunchKernelGGL(rotary_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, y, cosv, sinv, total, H, P, HD / 2, per_head);
+  VITPE_CHECK_LAUNCH();
+}
 
 static constexpr int ROTARY_BWD_MAX_SLICES = 64;   // include/vitpe.h: workspace of vitpe_apply_rotary_bwd
 

@@ -30,6 +30,7 @@ from . import ddp
 from . import kernels as K
 from .positional_encoding import (AbsolutePositionalEncoding, PolynomialRPE, RelativePositionalEncoding, RoPEAxial,
                                   RoPEMixed)
+from .head import StepHead
 from .optim import StepOptimizer
 from .route import (ALIGN, KIND_FRAG, KIND_FRAG_PHI, KIND_QKV, KIND_QKV_WIDE, KIND_T, Route, resolve_route,  # noqa: F401
                     shadow_plan)
@@ -111,8 +112,6 @@ class TrainEngine:
                                           extras=extras, fuse_ln=fuse_ln)
         self.__dict__.update(dataclasses.asdict(self.route))
         self._save_hidden = True
-        self._ticked = False                               # _loss(tick=True) on the fused head advanced the step counter
-        self._eval_ctl = self._eval_ctl_key = None         # eval_loss's scalars, per distinct batch shape
         self._build_flat(lr, weight_decay, betas, eps)
         self._build_buffers()
         self._build_rng_table()
@@ -363,24 +362,20 @@ class TrainEngine:
             self.act.append(dict(xn1=xn(), m1=f(M), r1=f(M), a=e(B, N, D), xmid=e(B, N, D), xn2=xn(),
                                  m2=f(M), r2=f(M), h=e(M, self.hid), u=e(M, self.hid),
                                  hd=e(M, self.hid) if self.extras and blk.mlp.drop > 0. else None))
-        self.logits, self.dlogits = f(B, self.Cn), f(B, self.Cn)
-        self.out2 = f(2)
-        self.metric_acc = torch.zeros(2, dtype=torch.float32, device=dev)  # [sum of batch-mean losses, #correct]
-        # cross-entropy scalars live on the device so a captured step follows a ragged last batch (train.py:89-90):
-        # {grad_scale, loss_scale, n_valid}; see set_valid()
-        self.ce_ctl = torch.zeros(4, dtype=torch.float32, device=dev)
-        self._valid = None
-        self.set_valid(B)
-        self.head_scratch = torch.zeros(2 * B, dtype=torch.float32, device=dev)   # (loss, correct) per image
-        self.head_ws = (f(B, D), f(B, D), f(B))
         self._probe_scratch = None
-        self.ws_dyn = f(B, D)
         # Gradient tensors read by the weight-gradient GEMMs get per-layer buffers (dy = d x_out, dmid = d x_mid,
         # du, dqkv): the grouped weight-gradient launch at the end of a backward part reads all of them, so the main
         # chain must not reuse one across layers (288 GB of HBM: ~0.7 GB extra is free)
         self.dtmp = e(B, N, D)
         self.dx_out = [e(B, N, D) for _ in range(self.Lyr + 1)]   # [l] = gradient w.r.t. x[l]
-        self.dx_out[self.Lyr].zero_()   # only its class rows are ever written (head): rows 1.. stay zero
+        # final norm + classifier + loss + metrics: head.StepHead (it also zeroes dx_out[L], whose rows 1.. nothing writes);
+        # logits, dlogits, out2 and metric_acc stay reachable here under their old names
+        mdl, G = self.model, self.Gr
+        self.head = StepHead(mdl.norm, mdl.head, (G(mdl.head.weight), G(mdl.head.bias), G(mdl.norm.weight), G(mdl.norm.bias)),
+                             self.x[self.Lyr], self.dx_out[self.Lyr], self.labels, self.hp, T, N, self.fuse_head, self.world,
+                             self.pg)
+        self.logits, self.dlogits, self.out2, self.metric_acc = (self.head.logits, self.head.dlogits, self.head.out2,
+                                                                 self.head.metric_acc)
         self.dx_mid = [e(B, N, D) for _ in range(self.Lyr)]
         self.du_l = [e(M, self.hid) for _ in range(self.Lyr)]
         self.dqkv_l = [e(B, N, 3 * D) for _ in range(self.Lyr)]
@@ -634,8 +629,7 @@ class TrainEngine:
         for l in range(self.Lyr):
             self._layer_fwd(l, train)
         if head:
-            K.head_fwd(self.x[-1], mdl.norm.weight.data, mdl.norm.bias.data, mdl.head.weight.data, mdl.head.bias.data,
-                       mdl.norm.eps, save=True, logits=self.logits, ws=self.head_ws)
+            self.head.forward()
 
     def _top_cls(self, l):
         return self.cls_rows and l == self.Lyr - 1
@@ -694,16 +688,7 @@ class TrainEngine:
 
     def _loss(self, tick=True):
         """tick: this loss belongs to a full step -- the fused head launch also advances the optimizer's step counter."""
-        self._ticked = bool(tick and self.fuse_head)
-        if self.fuse_head:   # final LayerNorm + head + CE + accuracy + dlogits + the head's backward: one launch pair
-            mdl, G = self.model, self.Gr
-            K.head_step(self.x[-1], mdl.norm.weight.data, mdl.norm.bias.data, mdl.head.weight.data, mdl.head.bias.data,
-                        self.labels, self.logits, self.dlogits, self.head_ws, self.ws_dyn, self.dx_out[self.Lyr], self.out2,
-                        self.metric_acc, self.head_scratch, self.ce_ctl, G(mdl.head.weight), G(mdl.head.bias),
-                        G(mdl.norm.weight), G(mdl.norm.bias), eps=mdl.norm.eps, hp_tick=(self.hp if tick else None))
-            return
-        K.cross_entropy_ctl(self.logits, self.labels, self.ce_ctl, dlogits=self.dlogits, out2=self.out2,
-                            metric_acc=self.metric_acc)
+        self.head.loss(tick)
 
     def _wgrad_problems(self, l):
         """Layer l's four nn.Linear weight gradients as (dY, X, dW, dbias[, ln[, row_step]]), in launch order: the operands
@@ -764,9 +749,7 @@ class TrainEngine:
         mdl, G = self.model, self.Gr
         hi, lo = self._part_layers(part)
         if part != "lower" and not self.fuse_head:
-            K.head_bwd(self.dlogits, mdl.head.weight.data, mdl.norm.weight.data, self.head_ws, self.T, self.N,
-                       G(mdl.head.weight), G(mdl.head.bias), G(mdl.norm.weight), G(mdl.norm.bias), dx=self.dx_out[self.Lyr],
-                       ws_dyn=self.ws_dyn)
+            self.head.backward()
         for l in range(hi, lo - 1, -1):
             self._layer_bwd(l, lo, hi)
         if part != "upper":
@@ -780,8 +763,8 @@ class TrainEngine:
             self._wgrad_group(part)
 
     def _optimizer(self):
-        self.opt.launch(self._ticked)
-        self._ticked = False
+        self.opt.launch(self.head.ticked)
+        self.head.ticked = False
         self.refresh_shadows(cast_flat=False)
         if self.extras:   # the step's last launch, after the backward has regenerated the forward's masks: the next step
             K.rng_advance(self.rng_table, 1)   # (or replay) draws new ones.  Once per step in every step shape
@@ -796,17 +779,9 @@ class TrainEngine:
 
     # ---------------------------------------------------------------- public API
     def set_valid(self, n_valid: int, n_valid_global: Optional[int] = None):
-        """The next steps' batches hold `n_valid` real samples in rows [0, n_valid) (the rest is padding) and the
-        GLOBAL batch (all ranks) holds `n_valid_global`.  Loss = mean over the global batch (train.py:113,194),
-        gradients = its gradient: dlogits are scaled by world / n_valid_global here and by 1 / world inside AdamW."""
-        if n_valid_global is None:
-            n_valid_global = n_valid * self.world
-        if not (0 <= n_valid <= self.B and n_valid_global >= max(n_valid, 1)):
-            raise L.VitpeError(f"set_valid({n_valid}, {n_valid_global}) with engine batch {self.B}")
-        if self._valid != (n_valid, n_valid_global):
-            self._valid = (n_valid, n_valid_global)
-            host = torch.tensor([self.world / n_valid_global, 1.0 / n_valid_global, float(n_valid), 0.0])
-            self.ce_ctl.copy_(host, non_blocking=False)
+        """Rows [0, n_valid) of the next steps' batches are real samples, `n_valid_global` over all ranks:
+        StepHead.set_valid."""
+        self.head.set_valid(n_valid, n_valid_global)
 
     def sync_from_model(self):
         """Re-derive every weight shadow (bf16 flat copy, transposed copies, packed qkv weights) from the fp32 master
@@ -825,8 +800,8 @@ class TrainEngine:
         """Warm up on a side stream, then capture forward+loss+backward (and, single-GPU, the
         optimizer) into HIP graphs.  Engine state is restored after the warm-up."""
         self.opt.guard("capture")
-        # everything the two warm-up steps move: the optimizer lists its own (StepOptimizer.state_tensors)
-        state = [self.flat_p, self.metric_acc, *self.opt.state_tensors(),
+        # everything the two warm-up steps move: the head and the optimizer list their own (state_tensors)
+        state = [self.flat_p, *self.head.state_tensors(), *self.opt.state_tensors(),
                  *(t for t in (self.rng_table, self.aug_rng) if t is not None)]
         snap = [t.clone() for t in state]
         s = torch.cuda.Stream()
@@ -1117,23 +1092,11 @@ class TrainEngine:
         return probes
 
     def eval_loss(self, n: int, acc: torch.Tensor, n_global: Optional[int] = None):
-        """acc[0] += (sum of the cross-entropy of rows [0, n) of the current logits vs self.labels) / n_global (this
-        rank's part of the batch mean, reference train.py:146-149; n_global defaults to n), acc[1] += #correct.
-        Device-side; leaves the training scalars untouched."""
-        key = (n, n_global or n)
-        if self._eval_ctl_key != key:   # (one host -> device copy per distinct batch shape, not per batch)
-            self._eval_ctl = torch.tensor([0.0, 1.0 / max(n_global or n, 1), float(n), 0.0], device=self.dev)
-            self._eval_ctl_key = key
-        K.cross_entropy_ctl(self.logits, self.labels, self._eval_ctl, dlogits=None, out2=self.out2, metric_acc=acc)
+        """acc[0] += this rank's part of the batch-mean cross-entropy of rows [0, n) of the current logits vs self.labels,
+        acc[1] += #correct, on the device: StepHead.eval_loss."""
+        self.head.eval_loss(n, acc, n_global)
 
     def read_metrics(self, reset=True):
-        """(sum over the steps since the last read of the global-batch mean loss, #correct over all ranks) -- the
-        ONLY host sync (and, data parallel, one 2-float all-reduce per read: every rank must call it)."""
-        t = self.metric_acc
-        if self.world > 1:
-            t = self.metric_acc.clone()
-            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.pg)
-        v = t.tolist()
-        if reset:
-            self.metric_acc.zero_()
-        return v[0], v[1]
+        """(sum since the last read of the global-batch mean loss, #correct over all ranks); the ONLY host sync:
+        StepHead.read_metrics."""
+        return self.head.read_metrics(reset)

@@ -2,7 +2,7 @@
 
 Same class names, constructor arguments, parameter / buffer names (state_dict keys) and
 method surface (`get_bias()`, `get_freqs_cis(seq_len, device)`, `.dim`, `.num_heads`) as
-the reference.  Tables are produced by HIP kernels (csrc/misc.hip); inside the
+the reference.  Tables are produced by HIP kernels (csrc/pe.hip); inside the
 model the fused attention kernel consumes the raw parameters directly and never
 materialises the [H,N,N] bias.
 """
