@@ -1,7 +1,8 @@
 """Measured figures of the LayerNorm-eps and head/loss GPU tests: every test collects (check, measured, limit) triples,
 appends them as one JSON line to profiles/ln_eps_head_parity.jsonl (the manner of _dump in test_bench_path_gpu.py; the
 committed file holds a passing run) and only THEN asserts, so a failing run leaves its numbers behind.  A module's worst
-figure per check is appended when the module finishes."""
+figure per check is appended when the module finishes.  A module may name another file under profiles/
+(Report(module, name): test_embed_gpu.py writes embed_parity.jsonl)."""
 import json
 import math
 import os
@@ -10,9 +11,10 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "ln_eps_head_parity.jsonl"
 
 
-def _append(line):
+def _append(line, name=None):
+    """name: the file under profiles/ (None: NAME, the file of the LayerNorm-eps and head/loss modules)"""
     os.makedirs(os.path.join(REPO, "profiles"), exist_ok=True)
-    with open(os.path.join(REPO, "profiles", NAME), "a") as f:
+    with open(os.path.join(REPO, "profiles", name or NAME), "a") as f:
         f.write(json.dumps(line) + "\n")
 
 
@@ -22,15 +24,15 @@ def _num(v):
 
 
 class Report:
-    def __init__(self, module):
-        self.module, self.worst = module, {}
+    def __init__(self, module, name=None):
+        self.module, self.worst, self.name = module, {}, name
 
     def case(self, test, case):
         return Case(self, test, case)
 
     def close(self):
         _append({"module": self.module, "worst": {k: {"measured": _num(v), "limit": _num(l), "at": at}
-                                                  for k, (v, l, at) in sorted(self.worst.items())}})
+                                                  for k, (v, l, at) in sorted(self.worst.items())}}, self.name)
 
 
 class Case:
@@ -61,5 +63,6 @@ class Case:
 
     def done(self):
         _append({"module": self.report.module, "test": self.test, "case": self.case_id,
-                 "figures": {k: _num(v) for k, v in self.figures.items()}, "missed": [list(map(str, b)) for b in self.bad]})
+                 "figures": {k: _num(v) for k, v in self.figures.items()}, "missed": [list(map(str, b)) for b in self.bad]},
+                self.report.name)
         assert not self.bad, f"{self.test}[{self.case_id}]: (check, measured, limit) missed: {self.bad}"

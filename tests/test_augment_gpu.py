@@ -144,7 +144,12 @@ def test_fused_embed_with_rng(K, C, S, p, D, pad, dt):
 
 
 # ---- 4. unaugmented identity ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("C,S,p,D", [(3, 32, 4, 192), (3, 16, 8, 96)])
+# whether the fused kernel has the geometry: K = 192 is outside it (that case keeps only its unfold half), K = 64 at p = 8 is
+# its generic gather branch
+NO_CROP_FUSED = {(3, 32, 4, 192): True, (3, 16, 8, 96): False, (1, 16, 8, 96): True}
+
+
+@pytest.mark.parametrize("C,S,p,D", list(NO_CROP_FUSED))
 def test_without_crop_and_flip_nothing_changes(K, C, S, p, D):
     from vitpe import _lib as L
     x, xd, mean, std = dataset(C, S)
@@ -161,7 +166,8 @@ def test_without_crop_and_flip_nothing_changes(K, C, S, p, D):
     assert torch.equal(off, plain) and torch.equal(null, plain) and torch.equal(img1, img0) and torch.equal(img2, img0)
     assert np.array_equal(img0.cpu().numpy(), A.images(x, INDEX, *STATS[C], (1, 2), 0, False))
     # patch_embed (where the fused kernel has the geometry)
-    if K.patch_embed_supported(dt, C, S, p, D):
+    assert K.patch_embed_supported(dt, C, S, p, D) == NO_CROP_FUSED[(C, S, p, D)]
+    if NO_CROP_FUSED[(C, S, p, D)]:
         g = torch.Generator().manual_seed(1)
         w = (torch.randn(D, Kp, generator=g) * 0.2).cuda().to(dt)
         bias, cls = torch.randn(D, generator=g).cuda(), torch.randn(D, generator=g).cuda()
