@@ -111,8 +111,7 @@ typedef __attribute__((ext_vector_type(4))) unsigned t2_u32x4;
 
 // 16-B store of a tile pair: lane (c, g) holds features 16nt + 4g + r (r < 4) of token c for two adjacent tiles; one
 // v_permlane16_swap per dword gives every lane 8 CONTIGUOUS features (see attn.hip)
-template <int AUX>
-VITPE_DEV void t2_store_pair(const T2Row& row, int nt0, int g, const f32x4& o0, const f32x4& o1) {
+VITPE_DEV t2_u32x4 t2_pack_pair(const f32x4& o0, const f32x4& o1) {
   uint32_t lo[2], hi[2];
 #pragma unroll
   for (int w2 = 0; w2 < 2; ++w2) {
@@ -122,8 +121,38 @@ VITPE_DEV void t2_store_pair(const T2Row& row, int nt0, int g, const f32x4& o0, 
     const auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(uint32_t, pa), __builtin_bit_cast(uint32_t, pb), false, false);
     lo[w2] = r[0]; hi[w2] = r[1];
   }
+  return (t2_u32x4){lo[0], lo[1], hi[0], hi[1]};
+}
+template <int AUX>
+VITPE_DEV void t2_store_pair(const T2Row& row, int nt0, int g, const f32x4& o0, const f32x4& o1) {
   const int f0 = 16 * (nt0 + (g & 1)) + 8 * (g >> 1);
-  __builtin_amdgcn_raw_buffer_store_b128((t2_u32x4){lo[0], lo[1], hi[0], hi[1]}, row.rsrc, row.off + 2 * f0, 0, AUX);
+  __builtin_amdgcn_raw_buffer_store_b128(t2_pack_pair(o0, o1), row.rsrc, row.off + 2 * f0, 0, AUX);
+}
+
+// Whole 128-byte lines instead of 16 rows x 64 B per instruction.  A 64-wide chunk of a row is one line = eight 16-B
+// pieces; lane (c, g) works on the pieces 2 (g & 1) + (g >> 1) of both 32-wide halves of ITS row c (t2_store_pair's
+// mapping).  Line-shaped, the chunk moves as two instructions j = 0, 1 in which lane (c, g) addresses row 2 (c >> 1) + j,
+// piece 4 (c & 1) + 2 (g & 1) + (g >> 1): the eight lanes of a token pair x four groups cover one line, an instruction
+// covers 8 rows.  Of the two pieces a lane moves, one belongs to its own row and one to the neighbouring token lane
+// c ^ 1's, so a quad_perm [1,0,3,2] DPP move and a select per dword turn the two forms into each other:
+//   (own row's half 0, own row's half 1)  <->  (instruction 0's piece, instruction 1's piece)
+// -- the same function in both directions (an involution), no LDS, no ds_bpermute.
+VITPE_DEV void t2_line_xchg(bool even, const t2_u32x4& a, const t2_u32x4& b, t2_u32x4& o0, t2_u32x4& o1) {
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const uint32_t na = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)a[w], 0xB1, 0xf, 0xf, true);
+    const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b[w], 0xB1, 0xf, 0xf, true);
+    o0[w] = even ? a[w] : nb;
+    o1[w] = even ? na : b[w];
+  }
+}
+// B fragments of two adjacent 32-deep k steps (natural k order: lane (c, g) holds elements 8g .. 8g + 7 of each) loaded as
+// the two lines of the 64-deep chunk they form -- row 2 (c >> 1) + j at piece 4 (c & 1) + g -- turned into the fragments
+VITPE_DEV void t2_lines_to_frags(bool even, Frag<bf16>& f0, Frag<bf16>& f1) {
+  t2_u32x4 o0, o1;
+  t2_line_xchg(even, __builtin_bit_cast(t2_u32x4, f0.v), __builtin_bit_cast(t2_u32x4, f1.v), o0, o1);
+  f0.v = __builtin_bit_cast(bf16x8, o0);
+  f1.v = __builtin_bit_cast(bf16x8, o1);
 }
 
 // The same for gelu'(u), kept as IEEE half (round toward zero, v_cvt_pkrtz_f16_f32: one instruction per pair like the bf16
@@ -614,7 +643,8 @@ __global__ __launch_bounds__(T2F_THREADS) void block_tail2_fwd_kernel(Tail2Args 
 // Backward of the block tail w.r.t. its inputs (the weight gradients are the grouped wgrad kernel's): the same pipeline on
 // the transposed weights.  Per 16-token tile, everything transposed ([feature][token] accumulators):
 //   dh  = dy W2            F1 stage: A = fc2.weight^T rows of the hidden sub-chunk (acc_to_frag k order), B = dy fragments
-//   du  = dh * gelu'(u)    G stage: gp rows loaded 2 sub-chunks ahead, du rows stored (fc1's weight gradient reads them)
+//   du  = dh * gelu'(u)    G stage: gp rows loaded 2 sub-chunks ahead, du rows stored (fc1's weight gradient reads them);
+//                          both a whole 64-wide chunk at a time, as 128-byte lines (t2_line_xchg)
 //   dxn = du W1            F2 stage: A = fc1.weight^T (k = hidden sub-chunk, acc_to_frag order), B = du fragments
 //   dx_mid = dy + LayerNorm2'(dxn)   (row statistics saved by the forward; dgamma / dbeta: DPP row sums over the 16 tokens,
 //                                     LDS atomics per workgroup, one global atomic per column and workgroup)
@@ -677,6 +707,31 @@ VITPE_DEV void t2_unpack_pair_f16(const Chunk16& v, f32x4& o0, f32x4& o1) {
   }
 }
 
+// A tile's 192-wide rows in the accumulator layout, packed (v[nt] = features 16nt + 4g .. + 3 of token c), loaded as lines
+// (t2_line_xchg): three lines per row, two instructions each, instead of twelve 8-byte pieces of the lane's own row.
+// `line`: row 2 (c >> 1) of the tile (clamped) + 32 (c & 1) + 16 (g & 1) + 8 (g >> 1), `step`: elements to the pair's second row.
+// After the exchange a lane holds the 16-B pieces t2_store_pair would write for its row: t2_unpack_pair's swap, kept packed.
+VITPE_DEV void t2_load_rows(bool even, const bf16* line, int step, bf16x4 (&v)[T2_NT]) {
+  Chunk16 l[6];
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+    l[2 * m] = *reinterpret_cast<const Chunk16*>(line + 64 * m);
+    l[2 * m + 1] = *reinterpret_cast<const Chunk16*>(line + step + 64 * m);
+  }
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+    Chunk16 h[2];
+    t2_line_xchg(even, l[2 * m], l[2 * m + 1], h[0], h[1]);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const auto r0 = __builtin_amdgcn_permlane16_swap(h[s][0], h[s][2], false, false);
+      const auto r1 = __builtin_amdgcn_permlane16_swap(h[s][1], h[s][3], false, false);
+      v[4 * m + 2 * s] = __builtin_bit_cast(bf16x4, (uint2){r0[0], r1[0]});
+      v[4 * m + 2 * s + 1] = __builtin_bit_cast(bf16x4, (uint2){r0[1], r1[1]});
+    }
+  }
+}
+
 // Column sums of 8 values over the 16 lanes of a DPP row (the 16 tokens of a tile) as a halving butterfly: each step a
 // lane keeps half of its values and adds its partner's copy of that half (partners: lane ^ 8, 7 - lane within the 8, ^ 2,
 // ^ 1), 15 DPP moves instead of 32.  Lane c ends with the total of value 4 b3 + 2 b2 + b1 (bits of c; b0 ignored).
@@ -697,13 +752,14 @@ VITPE_DEV float t2_colsum8(const float (&t)[8], int c) {
 // LayerNorm backward + residual on a transposed 16-token tile: acc = gradient w.r.t. the LayerNorm's OUTPUT on entry,
 //   acc <- res + rstd (gy - mean_f(gy) - xhat mean_f(gy xhat)),  gy = acc gamma,  xhat = (x - mean) rstd
 // rounded to the bf16 values stored to `orow`; the tile's dgamma / dbeta column sums (rows past M masked by `valid`) go to
-// the workgroup's LDS accumulators sAcc[0..191 | 192..383].  xrow / rrow: this lane's LayerNorm-input / residual row + 4g.
-VITPE_DEV void t2_ln_backward(f32x4 (&acc)[T2_NT], const bf16* xrow, const bf16* rrow, float mean, float rstd,
+// the workgroup's LDS accumulators sAcc[0..191 | 192..383].  xline / rline, lstep: the LayerNorm-input / residual rows as
+// t2_load_rows takes them.
+VITPE_DEV void t2_ln_backward(f32x4 (&acc)[T2_NT], const bf16* xline, const bf16* rline, int lstep, float mean, float rstd,
                               const float* sGam, float* sAcc, int c, int g, float valid, const T2Row& orow) {
   constexpr int D = T2_D, NT = T2_NT;
+  const bool even = (c & 1) == 0;
   bf16x4 xmv[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) xmv[nt] = *reinterpret_cast<const bf16x4*>(xrow + 16 * nt);
+  t2_load_rows(even, xline, lstep, xmv);
   const float invD = 1.0f / (float)D;
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -730,8 +786,7 @@ VITPE_DEV void t2_ln_backward(f32x4 (&acc)[T2_NT], const bf16* xrow, const bf16*
   }
   const float m1 = t2_xg_sum(s1) * invD, m2 = t2_xg_sum(s2) * invD;
   bf16x4 rv[NT];                                   // the residual rows
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) rv[nt] = *reinterpret_cast<const bf16x4*>(rrow + 16 * nt);
+  t2_load_rows(even, rline, lstep, rv);
   // second pass: gy and xhat are recomputed from the packed rows (keeping 48 fp32 xhat values alive across the row sums
   // is what spilled); the empty asm stops the compiler from re-using the first pass's conversions
 #pragma unroll
@@ -873,20 +928,32 @@ __global__ __launch_bounds__(T2_THREADS) void block_tail2_bwd_kernel(Tail2BwdArg
 
   // ---- compute waves -------------------------------------------------------------------------------------------------------
   Frag<T> bf[KS];
-  const T* const dqr = PRE ? reinterpret_cast<const T*>(a.dqkv) + (size_t)rowc * a.K1 + 8 * g : nullptr;
-  Frag<T> bqa[4], bqb[4];       // PRE: this wave's d_qkv rows as B fragments (natural k order), four 32-deep steps per slab
+  // Activation rows move as whole lines (t2_line_xchg): per 64-wide chunk this lane's two addresses are the rows 2 (c >> 1)
+  // and 2 (c >> 1) + 1 of the tile, clamped like rowc (row M - 1 again past the end: the same values at the same address);
+  // the second row is `lnext` rows after the first (0 or 1)
+  const bool even = (c & 1) == 0;
+  const int lrow = min(row & ~1, a.M - 1), lnext = min((row & ~1) + 1, a.M - 1) - lrow;
+  const T* const dql = PRE ? reinterpret_cast<const T*>(a.dqkv) + (size_t)lrow * a.K1 + 32 * (c & 1) + 8 * g : nullptr;
+  const int dqstep = PRE ? lnext * a.K1 : 0;
+  // ... and for the rows t2_store_pair wrote: piece 4 (c & 1) + 2 (g & 1) + (g >> 1) (its order inside a 32-wide half)
+  const int lpiece = 32 * (c & 1) + 16 * (g & 1) + 8 * (g >> 1);
+  const size_t lrowD = (size_t)lrow * D + lpiece;              // this lane's line address in a [M, 192] tensor
+  // PRE: this wave's d_qkv rows as B fragments (natural k order), four 32-deep steps = two 64-deep chunks per slab, loaded
+  // as lines (fragments 2h, 2h + 1 = the two lines of chunk h until qslab turns them into the k steps)
+  Frag<T> bqa[4], bqb[4];
+  auto ld_qlines = [&](Frag<T> (&f)[4], int q) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) f[i] = ld_frag(dql + (i & 1) * dqstep + 64 * min(2 * q + (i >> 1), nkc - 1));
+  };
   if (active) {
     if (PRE) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) bqa[i] = ld_frag(dqr + 32 * min(i, a.K1 / 32 - 1));
+      ld_qlines(bqa, 0);
     } else {
       // dy rows as B fragments in the acc_to_frag k order (what the PRE path produces from its accumulators)
-      const T* dr = reinterpret_cast<const T*>(a.dy) + (size_t)rowc * D + 4 * g;
+      bf16x4 dv[NT];
+      t2_load_rows(even, reinterpret_cast<const T*>(a.dy) + lrowD, lnext * D, dv);
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const bf16x4 lo = *reinterpret_cast<const bf16x4*>(dr + 32 * ks), hi = *reinterpret_cast<const bf16x4*>(dr + 32 * ks + 16);
-        bf[ks].v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-      }
+      for (int ks = 0; ks < KS; ++ks) bf[ks].v = __builtin_shufflevector(dv[2 * ks], dv[2 * ks + 1], 0, 1, 2, 3, 4, 5, 6, 7);
     }
   }
   __builtin_amdgcn_s_waitcnt(0x0070);           // vmcnt(0) lgkmcnt(0)
@@ -899,11 +966,10 @@ __global__ __launch_bounds__(T2_THREADS) void block_tail2_bwd_kernel(Tail2BwdArg
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int nks = a.K1 / 32;
-    auto qslab = [&](int q, const Frag<T> (&cur)[4], Frag<T> (&nxt)[4]) {
-      if (q + 1 < Q) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) nxt[i] = ld_frag(dqr + 32 * min(4 * (q + 1) + i, nks - 1));
-      }
+    auto qslab = [&](int q, Frag<T> (&cur)[4], Frag<T> (&nxt)[4]) {
+      if (q + 1 < Q) ld_qlines(nxt, q + 1);
+      t2_lines_to_frags(even, cur[0], cur[1]);
+      t2_lines_to_frags(even, cur[2], cur[3]);
       wait_ready(q);
       const T* wb = slab_ptr(q);
       t2_gemm<NT, 2, 8>(wb, cur, acc);
@@ -914,32 +980,55 @@ __global__ __launch_bounds__(T2_THREADS) void block_tail2_bwd_kernel(Tail2BwdArg
       qslab(q, bqa, bqb);
       if (q + 1 < Q) qslab(q + 1, bqb, bqa);
     }
-    t2_ln_backward(acc, reinterpret_cast<const T*>(a.x1) + (size_t)rowc * D + 4 * g,
-                   reinterpret_cast<const T*>(a.dres1) + (size_t)rowc * D + 4 * g, a.mean1[rowc], a.rstd1[rowc], sGam1, sAcc1,
-                   c, g, valid, t2_row(const_cast<void*>(a.dy), 16 * tile0, rowc, D));
+    t2_ln_backward(acc, reinterpret_cast<const T*>(a.x1) + lrowD, reinterpret_cast<const T*>(a.dres1) + lrowD, lnext * D,
+                   a.mean1[rowc], a.rstd1[rowc], sGam1, sAcc1, c, g, valid, t2_row(const_cast<void*>(a.dy), 16 * tile0, rowc, D));
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) bf[ks] = acc_to_frag<T>(acc[2 * ks], acc[2 * ks + 1]);
   }
 
-  const T* const gpr = reinterpret_cast<const T*>(a.gp) + (size_t)rowc * HID + 16 * (g & 1) + 8 * (g >> 1);
-  const T2Row dur = t2_row(a.du, 16 * tile0, rowc, HID);
-  Chunk16 gq[2];                                 // gelu'(u) rows of sub-chunks t, t + 1 in flight (slot t & 1)
-#pragma unroll
-  for (int t = 0; t < 2; ++t) gq[t] = *reinterpret_cast<const Chunk16*>(gpr + 32 * t);
+  // gelu'(u) and du rows as lines
+  const int lstep = lnext * HID;
+  const T* const gpl = reinterpret_cast<const T*>(a.gp) + (size_t)lrow * HID + lpiece;
+  const T2Row dul = t2_row(a.du, 16 * tile0, lrow, HID) + lpiece;
+  Chunk16 gq[2];                                 // gelu'(u): the two lines of the next chunk in flight
+  gq[0] = *reinterpret_cast<const Chunk16*>(gpl);
+  gq[1] = *reinterpret_cast<const Chunk16*>(gpl + lstep);
+  Chunk16 godd;                                  // the current chunk's odd sub-chunk, this lane's row
+  t2_u32x4 duh;                                  // the even sub-chunk's packed du pair, held for the line stores
   f32x4 acc2[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) acc2[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   f32x4 aX[2], aY[2];
   Frag<T> hP, hQ;
   const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-  // G stage of sub-chunk t: du = dh * gelu'(u) -> stored, -> B fragment of the F2 product; refills its prefetch slot
-  auto gstage = [&](const f32x4 (&a1c)[2], Chunk16& slot, int t, Frag<T>& hnew) {
+  // G stage of a sub-chunk: du = dh * gelu'(u) -> B fragment of the F2 product, and stored.  The even sub-chunk of chunk p
+  // turns the two lines into this row's two halves and issues the loads of chunk p + 1 (two sub-chunks ahead, as before);
+  // the odd one turns the two packed du pairs into lines and stores them.
+  auto gstage_even = [&](const f32x4 (&a1c)[2], int p, Frag<T>& hnew) {
     f32x4 g0, g1, d0, d1;
-    t2_unpack_pair_f16(slot, g0, g1);
-    if (t + 2 < nsub) slot = *reinterpret_cast<const Chunk16*>(gpr + 32 * (t + 2));
+    Chunk16 cur;
+    t2_line_xchg(even, gq[0], gq[1], cur, godd);
+    if (p + 1 < nchunk) {
+      gq[0] = *reinterpret_cast<const Chunk16*>(gpl + 64 * (p + 1));
+      gq[1] = *reinterpret_cast<const Chunk16*>(gpl + lstep + 64 * (p + 1));
+    }
+    t2_unpack_pair_f16(cur, g0, g1);
 #pragma unroll
     for (int r = 0; r < 4; ++r) { d0[r] = a1c[0][r] * g0[r]; d1[r] = a1c[1][r] * g1[r]; }
-    t2_store_pair<T2_AUX_HID>(dur + 32 * t, 0, g, d0, d1);
+    duh = t2_pack_pair(d0, d1);
+    // (held packed: without the pin the conversions sink into the next step and d0 / d1 stay alive instead)
+    asm volatile("" : "+v"(duh));
+    hnew = acc_to_frag<T>(d0, d1);
+  };
+  auto gstage_odd = [&](const f32x4 (&a1c)[2], int p, Frag<T>& hnew) {
+    f32x4 g0, g1, d0, d1;
+    t2_unpack_pair_f16(godd, g0, g1);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { d0[r] = a1c[0][r] * g0[r]; d1[r] = a1c[1][r] * g1[r]; }
+    t2_u32x4 l0, l1;
+    t2_line_xchg(even, duh, t2_pack_pair(d0, d1), l0, l1);
+    __builtin_amdgcn_raw_buffer_store_b128(l0, dul.rsrc, dul.off + 128 * p, 0, T2_AUX_HID);
+    __builtin_amdgcn_raw_buffer_store_b128(l1, dul.rsrc, dul.off + 2 * lstep + 128 * p, 0, T2_AUX_HID);
     hnew = acc_to_frag<T>(d0, d1);
   };
   constexpr int NVB = 3, RB = T2_RB;    // VALU instructions of the G stage per MFMA (it is short: the step is matrix-pipe bound)
@@ -950,7 +1039,7 @@ __global__ __launch_bounds__(T2_THREADS) void block_tail2_bwd_kernel(Tail2BwdArg
     aX[0] = z4; aX[1] = z4;
     t2_step<true, false, 0, RB>(wb, wb, bf, aX, hQ, acc2, [&]() {});                                             // F1_0
     aY[0] = z4; aY[1] = z4;
-    t2_step<true, false, 2 * NVB, RB>(wb + 2 * KS * 512, wb, bf, aY, hQ, acc2, [&]() { gstage(aX, gq[0], 0, hP); });   // F1_1 G_0
+    t2_step<true, false, 2 * NVB, RB>(wb + 2 * KS * 512, wb, bf, aY, hQ, acc2, [&]() { gstage_even(aX, 0, hP); });   // F1_1 G_0
     signal_done(Q + 1);
   }
   for (int p = 1; p < nchunk; ++p) {
@@ -958,23 +1047,21 @@ __global__ __launch_bounds__(T2_THREADS) void block_tail2_bwd_kernel(Tail2BwdArg
     const T* wb = slab_ptr(Q + p);
     const T* w2b = wb + T2_HALF * 512;
     aX[0] = z4; aX[1] = z4;
-    t2_step<true, true, NVB, RB>(wb, w2b, bf, aX, hP, acc2, [&]() { gstage(aY, gq[1], 2 * p - 1, hQ); });
+    t2_step<true, true, NVB, RB>(wb, w2b, bf, aX, hP, acc2, [&]() { gstage_odd(aY, p - 1, hQ); });
     aY[0] = z4; aY[1] = z4;
-    t2_step<true, true, NVB, RB>(wb + 2 * KS * 512, w2b + NT * 512, bf, aY, hQ, acc2, [&]() { gstage(aX, gq[0], 2 * p, hP); });
+    t2_step<true, true, NVB, RB>(wb + 2 * KS * 512, w2b + NT * 512, bf, aY, hQ, acc2, [&]() { gstage_even(aX, p, hP); });
     signal_done(Q + p + 1);
   }
   wait_ready(Q + nchunk);
   {
     const T* w2b = slab_ptr(Q + nchunk) + T2_HALF * 512;
-    const int tl = nsub - 1;
-    t2_step<false, true, 2 * NVB, RB>(w2b, w2b, bf, aX, hP, acc2, [&]() { gstage(aY, gq[1], tl, hQ); });
+    t2_step<false, true, 2 * NVB, RB>(w2b, w2b, bf, aX, hP, acc2, [&]() { gstage_odd(aY, nchunk - 1, hQ); });
     t2_step<false, true, 0, RB>(w2b, w2b + NT * 512, bf, aX, hQ, acc2, [&]() {});                                  // F2_last
     signal_done(Q + nchunk + 1);
   }
   // ---- LayerNorm2 backward + residual: dx_mid = dy + LayerNorm2'(dxn) ------------------------------------------------------------
-  t2_ln_backward(acc2, reinterpret_cast<const T*>(a.xmid) + (size_t)rowc * D + 4 * g,
-                 reinterpret_cast<const T*>(a.dy) + (size_t)rowc * D + 4 * g, a.mean2[rowc], a.rstd2[rowc], sGam, sAcc, c, g,
-                 valid, t2_row(a.dxmid, 16 * tile0, rowc, D));
+  t2_ln_backward(acc2, reinterpret_cast<const T*>(a.xmid) + lrowD, reinterpret_cast<const T*>(a.dy) + lrowD, lnext * D,
+                 a.mean2[rowc], a.rstd2[rowc], sGam, sAcc, c, g, valid, t2_row(a.dxmid, 16 * tile0, rowc, D));
   // ---- da = dx_mid Wp ----------------------------------------------------------------------------------------------------------
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) bf[ks] = acc_to_frag<T>(acc2[2 * ks], acc2[2 * ks + 1]);
@@ -1081,18 +1168,24 @@ __global__ __launch_bounds__(T2_THREADS) void ln_bwd2_kernel(LnBwd2Args a) {
   asm volatile("s_barrier" ::: "memory");
   if (!active) return;
 
-  const T* const dr = reinterpret_cast<const T*>(a.dy) + (size_t)rowc * K + 8 * g;
+  // the dY rows as lines (t2_line_xchg, t2_lines_to_frags): fragments 2h, 2h + 1 are loaded as the two lines of the 64-deep
+  // chunk h of a slab -- rows 2 (c >> 1) and 2 (c >> 1) + 1 of the tile, clamped like rowc -- and turned into its k steps
+  const bool even = (c & 1) == 0;
+  const int lrow = min(row & ~1, a.M - 1), lnext = min((row & ~1) + 1, a.M - 1) - lrow, dstep = lnext * K;
+  const T* const dl = reinterpret_cast<const T*>(a.dy) + (size_t)lrow * K + 32 * (c & 1) + 8 * g;
   Frag<T> bfa[KS], bfb[KS];
+  auto ld_lines = [&](Frag<T> (&f)[KS], int sl) {
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) bfa[ks] = ld_frag(dr + 32 * ks);
+    for (int ks = 0; ks < KS; ++ks) f[ks] = ld_frag(dl + (ks & 1) * dstep + sl * D + 64 * (ks >> 1));
+  };
+  ld_lines(bfa, 0);
   f32x4 acc[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  auto chunk = [&](int sl, const Frag<T> (&cur)[KS], Frag<T> (&nxt)[KS]) {
-    if (sl + 1 < nslab) {
+  auto chunk = [&](int sl, Frag<T> (&cur)[KS], Frag<T> (&nxt)[KS]) {
+    if (sl + 1 < nslab) ld_lines(nxt, sl + 1);
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) nxt[ks] = ld_frag(dr + (sl + 1) * D + 32 * ks);
-    }
+    for (int ks = 0; ks < KS; ks += 2) t2_lines_to_frags(even, cur[ks], cur[ks + 1]);
     while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(&sReady[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < 2)
       __builtin_amdgcn_s_sleep(1);
     asm volatile("" ::: "memory");
@@ -1108,9 +1201,9 @@ __global__ __launch_bounds__(T2_THREADS) void ln_bwd2_kernel(LnBwd2Args a) {
     chunk(sl, bfa, bfb);
     if (sl + 1 < nslab) chunk(sl + 1, bfb, bfa);
   }
-  t2_ln_backward(acc, reinterpret_cast<const T*>(a.x) + (size_t)rowc * D + 4 * g,
-                 reinterpret_cast<const T*>(a.dres) + (size_t)rowc * D + 4 * g, a.mean[rowc], a.rstd[rowc], sGam, sAcc, c, g,
-                 valid, t2_row(a.dx, 16 * tile0, rowc, D));
+  const size_t lrowD = (size_t)lrow * D + 32 * (c & 1) + 16 * (g & 1) + 8 * (g >> 1);
+  t2_ln_backward(acc, reinterpret_cast<const T*>(a.x) + lrowD, reinterpret_cast<const T*>(a.dres) + lrowD, lnext * D,
+                 a.mean[rowc], a.rstd[rowc], sGam, sAcc, c, g, valid, t2_row(a.dx, 16 * tile0, rowc, D));
   t2_flush_colsums(sAcc, &sFin, ntile_wg, lane, a.dgamma, a.dbeta);
 }
 
