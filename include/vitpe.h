@@ -435,6 +435,36 @@ int vitpe_patch_embed_aug(int dtype, const float* img, const unsigned char* data
                           int p, int D, float eps, const unsigned long long* rng, int pad, int hflip,
                           vitpe_stream_t stream);
 int vitpe_augment_params(const unsigned long long* rng, int* out, int B, int pad, int hflip, vitpe_stream_t stream);
+/* Erasing stream: torchvision.transforms.RandomErasing(p, scale, ratio, value) after Normalize, on the OUTPUT pixel
+ * coordinates (after crop and flip), with timm's three fill modes, on the same pair.  Every draw is a Philox4x32-10 call with
+ * key = (lo32 seed, hi32 seed) and counter = (c0, c1, lo32 offset, hi32 offset); (c0, c1) = (b, 0) is the crop/flip call.
+ *   u(w)   = ((w >> 9) + 0.5f) 2^-23                        (exact in fp32, strictly inside (0, 1))
+ *   switch : slot b is erased iff (uint64)w3 < erase_thr, w3 the fourth word of the call (b, 0);
+ *            erase_thr = floor((double)(float)prob 2^32) computed by the caller: 0 off, 2^32 always
+ *   rectangle: up to 10 attempts a = 0..9, call (b, a + 1), fp32 without fused multiply-add:
+ *            area = (float)(S S) (smin + u(w0) (smax - smin)) ; r = expf(lmin + u(w1) (lmax - lmin))
+ *            h = (int)rintf(sqrtf(area r)) ; w = (int)rintf(sqrtf(area / r)) ; accepted iff h < S && w < S, then
+ *            i = mulhi32(w2, S - h + 1) ; j = mulhi32(w3, S - w + 1).  No accepted attempt: nothing is erased.
+ *            lmin = (float)log(rmin), lmax = (float)log(rmax), computed by the caller.
+ *   fill of output pixel (c, y, x), i <= y < i + h, j <= x < j + w (every other pixel is the crop/flip result, bit for bit):
+ *            erase_mode 0 const: 0.0f ;  1 rand: one normal per channel for the rectangle, call (b, 11) ;
+ *            2 pixel: one normal per pixel and channel, call (lo32 e, 0x80000000 | hi32 e), e = (b S + y) S + x ;
+ *            normal of channel c, k = c >> 1:  sqrtf(-2 logf(u(w[2k]))) * ((c & 1) ? sinf : cosf)(6.2831853f u(w[2k+1]))
+ * erase_thr <= 2^32, erase_mode 0..2 (1 and 2: C <= 4), 0 < smin <= smax <= 1, finite lmin <= lmax, else hipErrorInvalidValue
+ * (nothing is launched).  The erased value goes to `patches` and img_out alike.
+ * vitpe_unfold_u8_erase: vitpe_unfold_u8_aug + the erasing arguments.  erase_thr == 0: the _aug entry, bit for bit;
+ *   rng == NULL: the plain entry (the erasing arguments are then not looked at).  pad == 0 with hflip == 0 erases the
+ *   uncropped image.  The fused vitpe_patch_embed has no erasing entry: feed it the img_out of this one.
+ * vitpe_erase_params     : the draws themselves, out [B,5] int = (on, i, j, h, w) of slots 0..B-1 (DEVICE pointers), for tests.
+ * vitpe_erase_params_host: host only, the same function compiled for the CPU; rng and out are HOST pointers.            */
+int vitpe_unfold_u8_erase(int dtype, const unsigned char* data, const long long* index, const float* mean,
+                          const float* stdv, void* patches, float* img_out, int B, int C, int S, int p,
+                          const unsigned long long* rng, int pad, int hflip, unsigned long long erase_thr, int erase_mode,
+                          float smin, float smax, float lmin, float lmax, vitpe_stream_t stream);
+int vitpe_erase_params(const unsigned long long* rng, int* out, int B, int S, unsigned long long thr, float smin, float smax,
+                       float lmin, float lmax, vitpe_stream_t stream);
+int vitpe_erase_params_host(const unsigned long long* rng, int* out, int B, int S, unsigned long long thr, float smin,
+                            float smax, float lmin, float lmax);
 /* dcls[d] += sum_b dtok[b,0,d]; dape[p,d] += sum_b dtok[b,1+p,d] (NULL to skip);
  * dpatch [B*P,D] T = patch rows of dtok (input of the patch-embed weight gradient)            */
 int vitpe_embed_bwd(int dtype, const void* dtok, float* dcls, float* dape, void* dpatch, int B,

@@ -273,13 +273,22 @@ __global__ void unfold8_kernel(const float* __restrict__ img, bf16* __restrict__
 // order and written straight as the patch matrix; img_out (nullable) receives the fp32 image.
 // AUG (vitpe_unfold_u8_aug): the source pixel goes through the augmentation stream of augment.h (random crop with zero
 // padding + horizontal flip per batch slot b); the draw is repeated only when a thread moves on to another image.
-template <typename T, bool AUG>
+// ERASE (vitpe_unfold_u8_erase, on top of AUG): the erasing stream, drawn per thread with the same rule.
+struct EraseArgs {
+  unsigned long long thr;
+  int mode;
+  float smin, smax, lmin, lmax;
+};
+template <typename T, bool AUG, bool ERASE>
 __global__ void unfold_u8_kernel(const unsigned char* __restrict__ data, const long long* __restrict__ index,
                                  const float* __restrict__ mean, const float* __restrict__ stdv, T* __restrict__ patches,
                                  float* __restrict__ img_out, int B, int Cc, int S, int p,
-                                 const unsigned long long* __restrict__ rng, int pad, int hflip) {
+                                 const unsigned long long* __restrict__ rng, int pad, int hflip, EraseArgs ea) {
+  static_assert(AUG || !ERASE, "the erasing stream runs on top of the augmented gather");
   const int g = S / p, P = g * g, Kp = Cc * p * p;
   const long long total = (long long)B * P * Cc * p;
+  EraseDraw er = {0, 0, 0, 0, 0};
+  EraseFill fill = {};
   AugDraw aug = {0, 0, 0};
   int aug_b = -1;
   for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
@@ -296,7 +305,14 @@ __global__ void unfold_u8_kernel(const unsigned char* __restrict__ data, const l
     T* dst = patches + ((size_t)b * P + n) * Kp + ch * p * p + ky * p;
     const float m = mean[ch], sd = stdv[ch];
     if (AUG) {
-      if (b != aug_b) { aug = aug_draw(rng, (unsigned long long)b, pad, hflip); aug_b = b; }
+      if (b != aug_b) {
+        aug = aug_draw(rng, (unsigned long long)b, pad, hflip);
+        aug_b = b;
+        if (ERASE) {
+          er = erase_draw(rng, (unsigned long long)b, S, ea.thr, ea.smin, ea.smax, ea.lmin, ea.lmax);
+          if (er.on) fill = erase_fill(rng, (unsigned long long)b, ea.mode);
+        }
+      }
       const int sy = gy * p + ky + aug.oy - pad;
       const bool rowok = sy >= 0 && sy < S;
       const unsigned char* row = data + (size_t)rec * Cc * S * S + ((size_t)ch * S + (rowok ? sy : 0)) * S;
@@ -304,7 +320,9 @@ __global__ void unfold_u8_kernel(const unsigned char* __restrict__ data, const l
         const int sx = (aug.flip ? S - 1 - (gx * p + kx) : gx * p + kx) + aug.ox - pad;
         unsigned char u = 0;   // the zero padding
         if (rowok && sx >= 0 && sx < S) u = row[sx];
-        const float v = ((float)u / 255.0f - m) / sd;
+        float v = ((float)u / 255.0f - m) / sd;
+        if (ERASE && erase_inside(er, gy * p + ky, gx * p + kx))
+          v = erase_value(fill, (unsigned long long)b, S, gy * p + ky, gx * p + kx, ch);
         dst[kx] = from_f32<T>(v);
         if (img_out != nullptr) img_out[(size_t)b * Cc * S * S + pix + kx] = v;
       }
@@ -325,6 +343,15 @@ __global__ void augment_params_kernel(const unsigned long long* __restrict__ rng
   if (b >= B) return;
   const AugDraw d = aug_draw(rng, (unsigned long long)b, pad, hflip);
   out[3 * b] = d.oy; out[3 * b + 1] = d.ox; out[3 * b + 2] = d.flip;
+}
+
+// the erasing draws of the first B batch slots (tests): out [B,5] = (on, i, j, h, w)
+__global__ void erase_params_kernel(const unsigned long long* __restrict__ rng, int* __restrict__ out, int B, int S,
+                                    EraseArgs ea) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const EraseDraw d = erase_draw(rng, (unsigned long long)b, S, ea.thr, ea.smin, ea.smax, ea.lmin, ea.lmax);
+  out[5 * b] = d.on; out[5 * b + 1] = d.i; out[5 * b + 2] = d.j; out[5 * b + 3] = d.h; out[5 * b + 4] = d.w;
 }
 
 // patch-embed parameter gradients that are plain column sums of the token gradient:
@@ -350,6 +377,8 @@ __global__ void embed_bwd_kernel(const T* __restrict__ dtok, float* dcls, float*
 }  // namespace vitpe
 
 using namespace vitpe;
+
+static const EraseArgs ERASE_OFF = {0ull, ERASE_CONST, 0.02f, 0.33f, 0.0f, 0.0f};   // (valid arguments, switch off)
 
 extern "C" int vitpe_patch_embed_supported(int dtype, int C, int S, int p, int D) {
   if (!(dtype == 0 || dtype == 1) || C < 1 || p < 1 || S < p || S % p != 0) return 0;
@@ -420,22 +449,28 @@ extern "C" int vitpe_unfold(int dtype, const float* img, void* patches, int B, i
 
 static int launch_unfold_u8(int dtype, const unsigned char* data, const long long* index, const float* mean,
                             const float* stdv, void* patches, float* img_out, int B, int C, int S, int p,
-                            const unsigned long long* rng, int pad, int hflip, hipStream_t st) {
+                            const unsigned long long* rng, int pad, int hflip, const EraseArgs& ea, hipStream_t st) {
   VITPE_REQUIRE(data && mean && stdv && patches && B >= 0 && C > 0 && p > 0 && S % p == 0 && (dtype == 0 || dtype == 1));
+  VITPE_REQUIRE(rng == nullptr || erase_args_ok(ea.thr, ea.mode, C, ea.smin, ea.smax, ea.lmin, ea.lmax));
   VITPE_REQUIRE(rng == nullptr || (pad >= 0 && pad <= S));
   const long long total = (long long)B * (S / p) * (S / p) * C * p;
   if (total == 0) return 0;
   const unsigned blocks = (unsigned)min((total + 255) / 256, (long long)8192);
-  if (rng != nullptr) {
+  if (rng != nullptr && ea.thr != 0) {
     if (dtype == 1)
-      hipLaunchKernelGGL((unfold_u8_kernel<bf16, true>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (bf16*)patches, img_out, B, C, S, p, rng, pad, hflip);
+      hipLaunchKernelGGL((unfold_u8_kernel<bf16, true, true>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (bf16*)patches, img_out, B, C, S, p, rng, pad, hflip, ea);
     else
-      hipLaunchKernelGGL((unfold_u8_kernel<float, true>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (float*)patches, img_out, B, C, S, p, rng, pad, hflip);
+      hipLaunchKernelGGL((unfold_u8_kernel<float, true, true>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (float*)patches, img_out, B, C, S, p, rng, pad, hflip, ea);
+  } else if (rng != nullptr) {
+    if (dtype == 1)
+      hipLaunchKernelGGL((unfold_u8_kernel<bf16, true, false>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (bf16*)patches, img_out, B, C, S, p, rng, pad, hflip, ea);
+    else
+      hipLaunchKernelGGL((unfold_u8_kernel<float, true, false>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (float*)patches, img_out, B, C, S, p, rng, pad, hflip, ea);
   } else {
     if (dtype == 1)
-      hipLaunchKernelGGL((unfold_u8_kernel<bf16, false>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (bf16*)patches, img_out, B, C, S, p, rng, 0, 0);
+      hipLaunchKernelGGL((unfold_u8_kernel<bf16, false, false>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (bf16*)patches, img_out, B, C, S, p, rng, 0, 0, ea);
     else
-      hipLaunchKernelGGL((unfold_u8_kernel<float, false>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (float*)patches, img_out, B, C, S, p, rng, 0, 0);
+      hipLaunchKernelGGL((unfold_u8_kernel<float, false, false>), dim3(blocks), dim3(256), 0, st, data, index, mean, stdv, (float*)patches, img_out, B, C, S, p, rng, 0, 0, ea);
   }
   VITPE_CHECK_LAUNCH();
 }
@@ -443,14 +478,23 @@ static int launch_unfold_u8(int dtype, const unsigned char* data, const long lon
 extern "C" int vitpe_unfold_u8(int dtype, const unsigned char* data, const long long* index, const float* mean,
                                const float* stdv, void* patches, float* img_out, int B, int C, int S, int p,
                                hipStream_t st) {
-  return launch_unfold_u8(dtype, data, index, mean, stdv, patches, img_out, B, C, S, p, nullptr, 0, 0, st);
+  return launch_unfold_u8(dtype, data, index, mean, stdv, patches, img_out, B, C, S, p, nullptr, 0, 0, ERASE_OFF, st);
 }
 
 // the same with the augmentation stream (rng NULL: exactly vitpe_unfold_u8)
 extern "C" int vitpe_unfold_u8_aug(int dtype, const unsigned char* data, const long long* index, const float* mean,
                                    const float* stdv, void* patches, float* img_out, int B, int C, int S, int p,
                                    const unsigned long long* rng, int pad, int hflip, hipStream_t st) {
-  return launch_unfold_u8(dtype, data, index, mean, stdv, patches, img_out, B, C, S, p, rng, pad, hflip, st);
+  return launch_unfold_u8(dtype, data, index, mean, stdv, patches, img_out, B, C, S, p, rng, pad, hflip, ERASE_OFF, st);
+}
+
+// the same with the erasing stream on top (erase_thr 0: exactly vitpe_unfold_u8_aug; rng NULL: exactly vitpe_unfold_u8)
+extern "C" int vitpe_unfold_u8_erase(int dtype, const unsigned char* data, const long long* index, const float* mean,
+                                     const float* stdv, void* patches, float* img_out, int B, int C, int S, int p,
+                                     const unsigned long long* rng, int pad, int hflip, unsigned long long erase_thr,
+                                     int erase_mode, float smin, float smax, float lmin, float lmax, hipStream_t st) {
+  return launch_unfold_u8(dtype, data, index, mean, stdv, patches, img_out, B, C, S, p, rng, pad, hflip,
+                          EraseArgs{erase_thr, erase_mode, smin, smax, lmin, lmax}, st);
 }
 
 extern "C" int vitpe_augment_params(const unsigned long long* rng, int* out, int B, int pad, int hflip, hipStream_t st) {
@@ -458,6 +502,26 @@ extern "C" int vitpe_augment_params(const unsigned long long* rng, int* out, int
   if (B == 0) return 0;
   hipLaunchKernelGGL(augment_params_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, rng, out, B, pad, hflip);
   VITPE_CHECK_LAUNCH();
+}
+
+// the erasing draws: on the device, and the same function on the host (rng and out in host memory, no stream)
+extern "C" int vitpe_erase_params(const unsigned long long* rng, int* out, int B, int S, unsigned long long thr, float smin,
+                                  float smax, float lmin, float lmax, hipStream_t st) {
+  VITPE_REQUIRE(rng && B >= 0 && (out || B == 0) && S >= 1 && erase_args_ok(thr, ERASE_CONST, 1, smin, smax, lmin, lmax));
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(erase_params_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, rng, out, B, S,
+                     EraseArgs{thr, ERASE_CONST, smin, smax, lmin, lmax});
+  VITPE_CHECK_LAUNCH();
+}
+
+extern "C" int vitpe_erase_params_host(const unsigned long long* rng, int* out, int B, int S, unsigned long long thr,
+                                       float smin, float smax, float lmin, float lmax) {
+  VITPE_REQUIRE(rng && B >= 0 && (out || B == 0) && S >= 1 && erase_args_ok(thr, ERASE_CONST, 1, smin, smax, lmin, lmax));
+  for (int b = 0; b < B; ++b) {
+    const EraseDraw d = erase_draw(rng, (unsigned long long)b, S, thr, smin, smax, lmin, lmax);
+    out[5 * b] = d.on; out[5 * b + 1] = d.i; out[5 * b + 2] = d.j; out[5 * b + 3] = d.h; out[5 * b + 4] = d.w;
+  }
+  return 0;
 }
 
 extern "C" int vitpe_embed_bwd(int dtype, const void* dtok, float* dcls, float* dape, void* dpatch, int B, int Ntok,

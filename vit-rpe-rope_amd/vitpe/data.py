@@ -174,18 +174,22 @@ def epoch_global_batches(n_items: int, global_batch: int, epoch: int, seed: int 
 
 
 def augment_batch(dataset: ResidentDataset, idx: Optional[torch.Tensor], rng: torch.Tensor, crop_pad: int = 0,
-                  hflip: bool = False) -> torch.Tensor:
+                  hflip: bool = False, erase_prob: float = 0., erase_mode: str = "const", erase_scale=(0.02, 0.33),
+                  erase_ratio=(0.3, 3.3)) -> torch.Tensor:
     """Normalised, augmented images fp32 [B,C,S,S] of samples `idx` (int64 [B] on the device; None: the first records) for
     the module path (`model(images)`): RandomCrop(S, padding=crop_pad) + RandomHorizontalFlip (if hflip) between Resize
-    and ToTensor, on the augmentation stream of the pair `rng` ("Augmentation stream") -- the pixels the
-    engine's embed kernels see for the same pair.  One launch (kernels.unfold_u8's img_out); advance the pair between
-    batches with kernels.rng_advance."""
+    and ToTensor, on the augmentation stream of the pair `rng` ("Augmentation stream"), then
+    RandomErasing(erase_prob, erase_scale, erase_ratio) with timm's fill mode erase_mode after Normalize, on the erasing
+    stream of the same pair ("Erasing stream") -- the pixels the engine's embed kernels see for the same pair.
+    One launch (kernels.unfold_u8's img_out); advance the pair between batches with kernels.rng_advance."""
     from . import kernels as K
+    K._check_erase(erase_prob, erase_mode, erase_scale, erase_ratio, dataset.images.shape[1], "augment_batch")
     K._check_augment(rng, crop_pad, dataset.images.shape[2], "augment_batch")
     _, C, S, _ = dataset.images.shape
     B = idx.shape[0] if idx is not None else dataset.images.shape[0]
     images = torch.empty((B, C, S, S), dtype=torch.float32, device=dataset.device)
     with torch.cuda.device(dataset.device):   # (one patch per image: the patch matrix is the image itself, a scratch here)
         K.unfold_u8(dataset.images, idx, dataset.mean, dataset.std, S, torch.float32, img_out=images, rng=rng,
-                    crop_pad=crop_pad, hflip=hflip)
+                    crop_pad=crop_pad, hflip=hflip, erase_prob=erase_prob, erase_mode=erase_mode, erase_scale=erase_scale,
+                    erase_ratio=erase_ratio)
     return images

@@ -7,6 +7,7 @@ in Python; there is no fallback path.
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -711,11 +712,74 @@ def augment_params(rng, B, crop_pad=0, hflip=False):
     return out
 
 
-def unfold_u8(data, index, mean, std, patch, dtype, out=None, img_out=None, rng=None, crop_pad=0, hflip=False):
+ERASE_MODES = {"const": 0, "rand": 1, "pixel": 2}     # timm's names: fill 0 / one normal per channel / one per pixel and channel
+ERASE_SCALE, ERASE_RATIO = (0.02, 0.33), (0.3, 3.3)   # torchvision's defaults
+
+
+def _check_erase(prob, mode, scale, ratio, C, what):
+    """Arguments of the erasing stream ("Erasing stream"), checked before anything touches a device.
+    -> the C entries' tail (erase_thr, erase_mode, smin, smax, lmin, lmax)."""
+    try:
+        prob, (smin, smax), (rmin, rmax) = float(prob), (float(v) for v in scale), (float(v) for v in ratio)
+    except (TypeError, ValueError):
+        raise L.VitpeError(f"{what}: erase_prob must be a number, erase_scale and erase_ratio pairs of numbers") from None
+    if not 0.0 <= prob <= 1.0:
+        raise L.VitpeError(f"{what}: erase_prob must be in [0, 1], got {prob}")
+    if mode not in ERASE_MODES:
+        raise L.VitpeError(f"{what}: erase_mode must be one of {sorted(ERASE_MODES)}, got {mode!r}")
+    if not 0.0 < smin <= smax <= 1.0:
+        raise L.VitpeError(f"{what}: erase_scale must satisfy 0 < min <= max <= 1, got {(smin, smax)}")
+    if not (0.0 < rmin <= rmax and math.isfinite(rmax)):
+        raise L.VitpeError(f"{what}: erase_ratio must satisfy 0 < min <= max, got {(rmin, rmax)}")
+    if mode != "const" and C is not None and int(C) > 4:
+        raise L.VitpeError(f"{what}: erase_mode {mode!r} draws at most 4 channels per call, the images have {int(C)}")
+    thr = int(math.floor(ctypes.c_float(prob).value * 4294967296.0))     # floor((double)(float)prob 2^32)
+    return thr, ERASE_MODES[mode], smin, smax, math.log(rmin), math.log(rmax)
+
+
+def _erase_tail(rng, prob, mode, scale, ratio, C, what):
+    """None when every erasing argument is at its default (the caller then takes the entry it took before the erasing stream
+    existed), else the checked tail of the _erase entries."""
+    if prob == 0. and mode == "const" and tuple(scale) == ERASE_SCALE and tuple(ratio) == ERASE_RATIO:
+        return None
+    tail = _check_erase(prob, mode, scale, ratio, C, what)
+    if rng is None and tail[0] != 0:
+        raise L.VitpeError(f"{what}: erase_prob > 0 needs rng, the (seed, offset) pair of the augmentation site")
+    return tail if rng is not None else None
+
+
+def erase_params(rng, B, S, prob, scale=ERASE_SCALE, ratio=ERASE_RATIO, host=False):
+    """int32 [B, 5] = (on, i, j, h, w) of batch slots 0..B-1: the erasing stream's draws for the pair `rng` and image size S
+    (tests only: the product kernels make the same draws in registers).  host=True: the same function compiled for the CPU;
+    rng is then a pair of Python ints or a CPU int64 tensor of two words, the result a CPU tensor, no device is touched."""
+    thr, _, smin, smax, lmin, lmax = _check_erase(prob, "const", scale, ratio, None, "erase_params")
+    if int(S) < 1 or int(B) < 0:
+        raise L.VitpeError(f"erase_params: B >= 0 and S >= 1 required, got B = {B}, S = {S}")
+    if host:
+        words = [int(v) & 0xFFFFFFFFFFFFFFFF for v in (rng.reshape(-1).tolist() if isinstance(rng, torch.Tensor) else rng)]
+        if len(words) != 2:
+            raise L.VitpeError("erase_params: rng must hold two words (seed, offset)")
+        pair = (ctypes.c_ulonglong * 2)(*words)
+        out = torch.zeros((int(B), 5), dtype=torch.int32)
+        check(lib().vitpe_erase_params_host(ctypes.cast(pair, ctypes.c_void_p), out.data_ptr(), int(B), int(S), thr, smin, smax,
+                                            lmin, lmax), "vitpe_erase_params_host")
+        return out
+    _check_augment(rng, 0, None, "erase_params")
+    out = torch.empty((int(B), 5), dtype=torch.int32, device=rng.device)
+    check(lib().vitpe_erase_params(ptr(rng), ptr(out), int(B), int(S), thr, smin, smax, lmin, lmax, stream_ptr()),
+          "vitpe_erase_params")
+    return out
+
+
+def unfold_u8(data, index, mean, std, patch, dtype, out=None, img_out=None, rng=None, crop_pad=0, hflip=False,
+              erase_prob=0., erase_mode="const", erase_scale=ERASE_SCALE, erase_ratio=ERASE_RATIO):
     """Resident uint8 dataset [Ndata,C,S,S] + sample indices [B] int64 (None: the first rows) -> normalised
     patch matrix [B*P, C*p*p] (ToTensor + Normalize + unfold in one pass); img_out optionally gets the fp32 images.
     rng (a (seed, offset) pair): RandomCrop(S, padding=crop_pad) + RandomHorizontalFlip (if hflip) per batch slot, on the
-    augmentation stream, inside the same kernel; crop_pad / hflip are ignored without it."""
+    augmentation stream, inside the same kernel; crop_pad / hflip are ignored without it.
+    erase_prob > 0 (needs rng): RandomErasing(erase_prob, erase_scale, erase_ratio) with timm's fill mode erase_mode on top,
+    on the erasing stream of the same pair."""
+    erase = _erase_tail(rng, erase_prob, erase_mode, erase_scale, erase_ratio, data.shape[1], "unfold_u8")
     if rng is not None:
         _check_augment(rng, crop_pad, data.shape[2], "unfold_u8")
     require_device(data, index, mean, std, out, img_out)
@@ -726,6 +790,11 @@ def unfold_u8(data, index, mean, std, patch, dtype, out=None, img_out=None, rng=
     B = index.shape[0] if index is not None else data.shape[0]
     g = S // patch
     o = out if out is not None else torch.empty((B * g * g, C * patch * patch), dtype=dtype, device=data.device)
+    if erase is not None:
+        check(lib().vitpe_unfold_u8_erase(dtype_code(dtype), ptr(data), ptr(index), ptr(mean), ptr(std), ptr(o), ptr(img_out), B,
+                                          C, S, patch, ptr(rng), int(crop_pad), int(bool(hflip)), *erase, stream_ptr()),
+              "vitpe_unfold_u8_erase")
+        return o
     if rng is not None:
         check(lib().vitpe_unfold_u8_aug(dtype_code(dtype), ptr(data), ptr(index), ptr(mean), ptr(std), ptr(o), ptr(img_out), B,
                                         C, S, patch, ptr(rng), int(crop_pad), int(bool(hflip)), stream_ptr()),
