@@ -169,8 +169,9 @@ def test_attention_module_probs_ignore_dropout_and_mode(K):
 
 def test_attention_module_probs_with_caller_tables(K):
     from oracle import vit_oracle as O
+    from vitpe.positional_encoding import RoPEAxial
     N, hd = 26, 32
-    m = _attention().train()
+    m = _attention(RoPEAxial(hd, 10.0)).train()   # (a rotary module, the only kind that reads caller tables, vit.py:51; not its own theta)
     x = rnd(B, N, 64, seed=85)
     inv_freq = O.rope_axial_inv_freq(hd, 100.0)
     cos, sin = O.rope_axial_tables(N - 1, inv_freq)

@@ -380,7 +380,7 @@ def test_qkv_bias_alone_runs_without_dropout_kernels(K):
 
 
 def test_table_gradients_with_attn_drop_are_refused(K):
-    attn, _ = make_attention("none", 17, qkv_bias=False, attn_drop=0.1, proj_drop=0.)
+    attn, _ = make_attention("rope-axial", 17, qkv_bias=False, attn_drop=0.1, proj_drop=0.)   # (only a rotary module reads tables)
     attn.train()
     cos = torch.rand(16, 16, device="cuda").requires_grad_(True)
     sin = torch.rand(16, 16, device="cuda").requires_grad_(True)

@@ -146,6 +146,28 @@ def test_attention_module(golden, tag):
         assert rel_err(res[k], g[f"{tag}/{k}"]) < 5e-6, k
 
 
+@pytest.mark.parametrize("tag", ["none_tables", "relative_tables", "polynomial_tables", "rope-axial_none"])
+def test_attention_module_ignores_what_its_encoding_does_not_use(golden, tag):
+    """golden/attention_tables.npz: the reference's Attention handed constant (cos, sin) tables under pos_encoding None,
+    relative and polynomial -- nothing is rotated, the bias is still added (vit.py:51, 73-81) -- and RoPEAxial handed
+    freqs_cis=None -- plain attention.  The oracle under that rule reproduces y; rotating with the tables does not."""
+    g = golden("attention_tables")
+    D, H, B, N = 64, 2, 2, 17
+    CF = O.closed_form_tensor
+    wqkv, wproj, bproj = CF("attn.qkv.weight", (3 * D, D)), CF("attn.proj.weight", (D, D)), CF("attn.proj.bias", (D,))
+    x = CF("attn.x", (B, N, D)) * 20
+    bias = None
+    if tag == "relative_tables":
+        bias = O.relative_bias(CF("pos_embed.relative_position_bias_table", (H, 2 * N - 1)), N)
+    elif tag == "polynomial_tables":
+        bias = O.polynomial_bias(CF("pos_embed.coefficients", (4,)), N - 1, H, 3, True)
+    y = torch.nn.functional.linear(O.fused_attention(x, wqkv, H, None, bias), wproj, bproj)
+    assert rel_err(y.numpy(), g[f"{tag}/y"]) < FTOL
+    tabs = (torch.from_numpy(g["cos"]), torch.from_numpy(g["sin"]))
+    rotated = torch.nn.functional.linear(O.fused_attention(x, wqkv, H, tabs, bias), wproj, bproj)
+    assert rel_err(rotated.numpy(), g[f"{tag}/y"]) > 1e3 * FTOL
+
+
 @pytest.mark.parametrize("tag,extra", MODES)
 def test_small_model_logits_loss_grads(golden, tag, extra):
     g = golden("model")

@@ -14,7 +14,8 @@ code runs unmodified.  Consequently everything except the Mlp arithmetic is
 pinned by the reference itself; the Mlp boundary is "parity unpinned".
 
 Usage:  python tools/make_golden.py            (writes tests/golden/)
-        python tools/make_golden.py --only resize     (resize.npz alone, from PIL; also heads, rotary_grad)
+        python tools/make_golden.py --only resize     (resize.npz alone, from PIL; also heads, rotary_grad, dropout,
+                                                       attention_tables)
 """
 import importlib.util
 import os
@@ -241,6 +242,38 @@ def gen_attention(ref):
             out[f"{tag}/dpe.{n}"] = np_(p.grad)
     np.savez_compressed(os.path.join(OUT, "attention.npz"), **out)
     print("attention.npz", {k: v.shape for k, v in out.items()})
+
+
+TAB_DIM, TAB_H, TAB_B, TAB_N = 64, 2, 2, 17
+
+
+def gen_attention_tables(ref):
+    """The reference Attention.forward handed what its pos_encoding does not use (vit.py:51, 73-81): pos_encoding None,
+    RelativePositionalEncoding and PolynomialRPE each handed constant (cos, sin) tables -- never rotated, the bias still
+    added -- and RoPEAxial handed freqs_cis=None -- plain attention.  y alone, closed-form tensors as gen_attention."""
+    vit, pe = ref["vit"], ref["positional_encoding"]
+    D, H, B, N = TAB_DIM, TAB_H, TAB_B, TAB_N
+    hd = D // H
+    ang = torch.linspace(0.0, 2.5, (N - 1) * (hd // 2)).reshape(N - 1, hd // 2) ** 1.3   # angles up to 2.5 rad: no module's own
+    cos, sin = torch.cos(ang), torch.sin(ang)
+    out = {"cos": np_(cos), "sin": np_(sin)}
+    for tag in ("none_tables", "relative_tables", "polynomial_tables", "rope-axial_none"):
+        torch.manual_seed(0)
+        att = vit.Attention(D, num_heads=H)
+        pem = {"none_tables": None, "relative_tables": pe.RelativePositionalEncoding(N - 1, H),
+               "polynomial_tables": pe.PolynomialRPE(N - 1, 3, H, shared_across_heads=True),
+               "rope-axial_none": pe.RoPEAxial(hd, 100.0)}[tag]
+        att.set_pos_encoding(pem)
+        with torch.no_grad():
+            att.qkv.weight.copy_(O.closed_form_tensor("attn.qkv.weight", (3 * D, D)))
+            att.proj.weight.copy_(O.closed_form_tensor("attn.proj.weight", (D, D)))
+            att.proj.bias.copy_(O.closed_form_tensor("attn.proj.bias", (D,)))
+            for n, p in (pem.named_parameters() if pem is not None else ()):
+                p.copy_(O.closed_form_tensor("pos_embed." + n, tuple(p.shape)))
+            x = O.closed_form_tensor("attn.x", (B, N, D)) * 20
+            out[f"{tag}/y"] = np_(att(x, freqs_cis=None if tag == "rope-axial_none" else (cos, sin)))
+    np.savez_compressed(os.path.join(OUT, "attention_tables.npz"), **out)
+    print("attention_tables.npz", {k: v.shape for k, v in out.items()})
 
 
 SMALL = dict(embed_dim=96, depth=2, num_heads=3)
@@ -633,9 +666,14 @@ def main():
         gen_rotary_grad(ref)
         print("rotary_grad.npz", os.path.getsize(os.path.join(OUT, "rotary_grad.npz")), "bytes")
         return
+    if sys.argv[1:] == ["--only", "attention_tables"]:
+        gen_attention_tables(ref)
+        print("attention_tables.npz", os.path.getsize(os.path.join(OUT, "attention_tables.npz")), "bytes")
+        return
     gen_tables(ref)
     gen_rotary(ref)
     gen_attention(ref)
+    gen_attention_tables(ref)
     gen_model(ref)
     gen_heads(ref)
     gen_rotary_grad(ref)

@@ -6,6 +6,12 @@ autograd over ATen ops; here the gradients are explicit).  Parameters arrive as 
 masters; the compute type of the GEMMs follows the activation dtype (float32 = exact-fp32
 MFMA parity mode, bfloat16 = throughput mode) and weight shadows are produced on the fly.
 Parameter gradients are returned in fp32.
+
+Each hand-written backward is a custom op of its own (`vitpe::<op>_backward`, with a fake like the forward ops): the
+function handed to `register_autograd` has to be traceable, and one that hands data pointers to the library is not --
+under torch.compile / AOT autograd it would be run on fake tensors.  A custom op cannot return None, so a gradient that
+does not exist (no qkv bias, no PE parameter, constant tables) leaves a backward op as an empty tensor; `_opt` turns it
+back into None.
 """
 from __future__ import annotations
 
@@ -18,6 +24,14 @@ from . import _lib as L
 from . import kernels as K
 
 MODES = ["none", "absolute", "relative", "polynomial", "rope-axial", "rope-mixed"]
+
+
+def _opt(t: Tensor) -> Optional[Tensor]:
+    return None if t.numel() == 0 else t
+
+
+def _zeros(t: Tensor) -> Tensor:
+    return torch.zeros(t.shape, dtype=t.dtype, device=t.device)
 
 
 def _shadow(w: Tensor, dtype) -> Tensor:
@@ -53,10 +67,12 @@ def layer_norm(x: Tensor, weight: Tensor, bias: Tensor, eps: float) -> Tuple[Ten
     return y, mean, rstd
 
 
+# The fakes answer with what the real ops return: freshly allocated CONTIGUOUS tensors whatever the strides of the inputs
+# (every op works on x.contiguous(); torch.empty_like of a transposed input would keep its strides).
 @layer_norm.register_fake
-def _(x, weight, bias, eps):
+def layer_norm_fake(x, weight, bias, eps):
     m = x.numel() // x.shape[-1]
-    return torch.empty_like(x), x.new_empty(m, dtype=torch.float32), x.new_empty(m, dtype=torch.float32)
+    return x.new_empty(x.shape), x.new_empty(m, dtype=torch.float32), x.new_empty(m, dtype=torch.float32)
 
 
 def _ln_setup(ctx, inputs, output):
@@ -65,11 +81,22 @@ def _ln_setup(ctx, inputs, output):
     ctx.save_for_backward(x, weight, mean, rstd)
 
 
+@torch.library.custom_op("vitpe::layer_norm_backward", mutates_args=())
+def layer_norm_backward(dy: Tensor, x: Tensor, weight: Tensor, mean: Tensor, rstd: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (dx, dweight, dbias)"""
+    dg, db = _zeros(weight), _zeros(weight)
+    dx = K.layernorm_bwd(dy.contiguous(), x.contiguous(), mean, rstd, weight, dg, db)
+    return dx, dg, db
+
+
+@layer_norm_backward.register_fake
+def layer_norm_backward_fake(dy, x, weight, mean, rstd):
+    return x.new_empty(x.shape), weight.new_empty(weight.shape), weight.new_empty(weight.shape)
+
+
 def _ln_backward(ctx, dy, _dm, _dr):
     x, weight, mean, rstd = ctx.saved_tensors
-    dg = torch.zeros_like(weight)
-    db = torch.zeros_like(weight)
-    dx = K.layernorm_bwd(dy.contiguous(), x.contiguous(), mean, rstd, weight, dg, db)
+    dx, dg, db = torch.ops.vitpe.layer_norm_backward(dy, x, weight, mean, rstd)
     return dx, dg, db, None
 
 
@@ -134,10 +161,14 @@ def _attention_setup(ctx, output, one_kernel, xn, wqkv, bqkv, wproj, resid, num_
                 proj_p)
 
 
-def _attention_backward(ctx, dy):
-    """-> (dxn, dwqkv, dbqkv, dwproj, dbproj, dresid, dpe, dcos, dsin), the backward of both attention ops."""
-    xn, wqkv, wproj, a, qkv, pe_param, inv_freq, cos, sin, rng = ctx.saved_tensors
-    one_kernel, num_heads, mode, grid, degree, per_head, has_resid, tables_grad, has_bqkv, attn_p, proj_p = ctx.meta
+@torch.library.custom_op("vitpe::attention_backward", mutates_args=())
+def attention_backward(dy: Tensor, xn: Tensor, wqkv: Tensor, wproj: Tensor, a: Tensor, qkv: Tensor, pe_param: Optional[Tensor],
+                       inv_freq: Optional[Tensor], cos: Optional[Tensor], sin: Optional[Tensor], rng: Optional[Tensor],
+                       one_kernel: bool, num_heads: int, mode: int, grid: int, degree: int, per_head: bool, tables_grad: bool,
+                       has_bqkv: bool, attn_p: float, proj_p: float
+                       ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (dxn, dwqkv, dbqkv, dwproj, dbproj, dpe, dcos, dsin), the backward of both attention ops on what their forward
+    saved; the gradients that do not exist are empty tensors."""
     dt = xn.dtype
     B, N, D = xn.shape
     dy2 = dy.contiguous().view(B * N, D)
@@ -145,12 +176,12 @@ def _attention_backward(ctx, dy):
         dy2 = K.dropout_bwd(dy2, rng[1], proj_p)
     # proj: da = dy Wproj ; dWproj = dy^T a ; dbproj = colsum(dy)
     da = K.linear(dy2, _shadow_t(wproj, dt), None, epi=L.EPI_BIAS)
-    dwproj = torch.zeros_like(wproj)
+    dwproj = _zeros(wproj)
     dbproj = torch.zeros(D, dtype=torch.float32, device=dy.device)
     K.gemm_tn(dy2, a.view(B * N, D), dwproj, dbproj)
     # attention backward -> dqkv (+ PE parameter grads)
     t = _pe_tables(mode, grid, pe_param, inv_freq, degree, per_head, cos, sin)
-    dpe = torch.zeros_like(pe_param) if pe_param is not None else None
+    dpe = _zeros(pe_param) if pe_param is not None else None
     name = MODES[mode]
     pe_grads = dict(dtable=dpe if name == "relative" else None, dcoeff=dpe if name == "polynomial" else None,
                     dfreqs=dpe if name == "rope-mixed" else None)
@@ -171,10 +202,33 @@ def _attention_backward(ctx, dy):
         dqkv = K.attention_core_bwd(qkv, da.view(B, N, D), num_heads, t, **pe_grads)
     dq2 = dqkv.view(B * N, 3 * D)
     dxn = K.linear(dq2, _shadow_t(wqkv, dt), None, epi=L.EPI_BIAS).view(B, N, D)
-    dwqkv = torch.zeros_like(wqkv)
+    dwqkv = _zeros(wqkv)
     dbqkv = torch.zeros(3 * D, dtype=torch.float32, device=dy.device) if has_bqkv else None   # gemm_tn's dbias: colsum(dqkv)
     K.gemm_tn(dq2, xn.contiguous().view(B * N, D), dwqkv, dbqkv)
-    return dxn, dwqkv, dbqkv, dwproj, dbproj, dy if has_resid else None, dpe, dcos, dsin
+    dbqkv, dpe, dcos, dsin = (xn.new_empty(0) if g is None else g for g in (dbqkv, dpe, dcos, dsin))   # (one tensor each)
+    return dxn, dwqkv, dbqkv, dwproj, dbproj, dpe, dcos, dsin
+
+
+@attention_backward.register_fake
+def attention_backward_fake(dy, xn, wqkv, wproj, a, qkv, pe_param, inv_freq, cos, sin, rng, one_kernel, num_heads, mode, grid,
+                            degree, per_head, tables_grad, has_bqkv, attn_p, proj_p):
+    D = xn.shape[-1]
+    f32 = dict(dtype=torch.float32)
+    no_dpe = pe_param is None or (cos is not None and MODES[mode] == "rope-mixed")
+    tabs = tables_grad and attn_p == 0.0
+    return (xn.new_empty(xn.shape), wqkv.new_empty(wqkv.shape), xn.new_empty(3 * D, **f32) if has_bqkv else xn.new_empty(0),
+            wproj.new_empty(wproj.shape), xn.new_empty(D, **f32), xn.new_empty(0) if no_dpe else pe_param.new_empty(pe_param.shape),
+            cos.new_empty(cos.shape) if tabs else xn.new_empty(0), sin.new_empty(sin.shape) if tabs else xn.new_empty(0))
+
+
+def _attention_backward(ctx, dy):
+    """-> (dxn, dwqkv, dbqkv, dwproj, dbproj, dresid, dpe, dcos, dsin), the backward of both attention ops."""
+    xn, wqkv, wproj, a, qkv, pe_param, inv_freq, cos, sin, rng = ctx.saved_tensors
+    one_kernel, num_heads, mode, grid, degree, per_head, has_resid, tables_grad, has_bqkv, attn_p, proj_p = ctx.meta
+    dxn, dwqkv, dbqkv, dwproj, dbproj, dpe, dcos, dsin = torch.ops.vitpe.attention_backward(
+        dy, xn, wqkv, wproj, a, qkv, pe_param, inv_freq, cos, sin, rng, one_kernel, num_heads, mode, grid, degree, per_head,
+        tables_grad, has_bqkv, attn_p, proj_p)
+    return dxn, dwqkv, _opt(dbqkv), dwproj, dbproj, dy if has_resid else None, _opt(dpe), _opt(dcos), _opt(dsin)
 
 
 @torch.library.custom_op("vitpe::attention", mutates_args=())
@@ -192,10 +246,15 @@ def attention(xn: Tensor, wqkv: Tensor, wproj: Tensor, bproj: Tensor, resid: Opt
 
 
 @attention.register_fake
-def _(xn, wqkv, wproj, bproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos=None, sin=None,
-      tables_grad=False):
-    B, N, D = xn.shape
-    return torch.empty_like(xn), torch.empty_like(xn), xn.new_empty(0)
+def attention_fake(xn, wqkv, wproj, bproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos=None,
+                   sin=None, tables_grad=False):
+    """The branch of _attention_forward on the concrete shape (the route is a function of dtype, N, D and the head
+    dimension, so a trace specialises on them): `qkv` is empty where the kernel that keeps it on the chip runs (_fused_ok
+    and no table gradients), [B, N, 3D] on the hd-64 one-kernel route and on the qkv Linear + core route.  The backward
+    dispatches on qkv.numel() == 0."""
+    B, N, D = (int(s) for s in xn.shape)
+    on_chip = not tables_grad and bool(L.lib().vitpe_fused_attention_supported(L.dtype_code(xn.dtype), N, D, D // num_heads))
+    return xn.new_empty((B, N, D)), xn.new_empty((B, N, D)), xn.new_empty(0) if on_chip else xn.new_empty((B, N, 3 * D))
 
 
 def _attn_setup(ctx, inputs, output):
@@ -228,10 +287,10 @@ def attention_drop(xn: Tensor, wqkv: Tensor, bqkv: Optional[Tensor], wproj: Tens
 
 
 @attention_drop.register_fake
-def _(xn, wqkv, bqkv, wproj, bproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos, sin, tables_grad,
-      attn_p, proj_p, rng):
+def attention_drop_fake(xn, wqkv, bqkv, wproj, bproj, resid, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos,
+                        sin, tables_grad, attn_p, proj_p, rng):
     B, N, D = xn.shape
-    return torch.empty_like(xn), torch.empty_like(xn), xn.new_empty((B, N, 3 * D))
+    return xn.new_empty((B, N, D)), xn.new_empty((B, N, D)), xn.new_empty((B, N, 3 * D))
 
 
 def _attn_drop_setup(ctx, inputs, output):
@@ -262,7 +321,7 @@ def attention_probs(qkv: Tensor, num_heads: int, mode: int, grid: int, pe_param:
 
 
 @attention_probs.register_fake
-def _(qkv, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos=None, sin=None, cls_only=False):
+def attention_probs_fake(qkv, num_heads, mode, grid, pe_param, inv_freq, degree, per_head, cos=None, sin=None, cls_only=False):
     B, N, _ = qkv.shape
     shape = (B, num_heads, N) if cls_only else (B, num_heads, N, N)
     return qkv.new_empty(shape, dtype=torch.float32)
@@ -295,9 +354,9 @@ def mlp(xn: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, resid: Optio
 
 
 @mlp.register_fake
-def _(xn, w1, b1, w2, b2, resid, p=0.0, rng=None):
+def mlp_fake(xn, w1, b1, w2, b2, resid, p=0.0, rng=None):
     m = xn.numel() // xn.shape[-1]
-    return torch.empty_like(xn), xn.new_empty(m, w1.shape[0]), xn.new_empty(m, w1.shape[0])
+    return xn.new_empty(xn.shape), xn.new_empty(m, w1.shape[0]), xn.new_empty(m, w1.shape[0])
 
 
 def _mlp_setup(ctx, inputs, output):
@@ -308,24 +367,38 @@ def _mlp_setup(ctx, inputs, output):
     ctx.p = p
 
 
-def _mlp_backward(ctx, dy, _dh, _du):
-    xn, w1, w2, h, u, rng = ctx.saved_tensors
+@torch.library.custom_op("vitpe::mlp_backward", mutates_args=())
+def mlp_backward(dy: Tensor, xn: Tensor, w1: Tensor, w2: Tensor, h: Tensor, u: Tensor, rng: Optional[Tensor], p: float
+                 ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (dxn, dw1, db1, dw2, db2)"""
     dt = xn.dtype
     D = xn.shape[-1]
-    dres = dy if ctx.has_resid else None
     dy2 = dy.contiguous().view(-1, D)
     x2 = xn.contiguous().view(-1, D)
-    if ctx.p > 0.0:
-        dy2 = K.dropout_bwd(dy2, rng[1], ctx.p)
+    if p > 0.0:
+        dy2 = K.dropout_bwd(dy2, rng[1], p)
     du = K.linear(dy2, _shadow_t(w2, dt), None, epi=L.EPI_GELU_BWD, u=u)
-    if ctx.p > 0.0:   # (dy W2) . m1 / (1-p) . gelu'(u): the two elementwise factors commute
-        du = K.dropout_bwd(du, rng[0], ctx.p)
-    dw2, db2 = torch.zeros_like(w2), torch.zeros(w2.shape[0], dtype=torch.float32, device=dy.device)
+    if p > 0.0:   # (dy W2) . m1 / (1-p) . gelu'(u): the two elementwise factors commute
+        du = K.dropout_bwd(du, rng[0], p)
+    dw2, db2 = _zeros(w2), torch.zeros(w2.shape[0], dtype=torch.float32, device=dy.device)
     K.gemm_tn(dy2, h, dw2, db2)
     dxn = K.linear(du, _shadow_t(w1, dt), None, epi=L.EPI_BIAS).view(xn.shape)
-    dw1, db1 = torch.zeros_like(w1), torch.zeros(w1.shape[0], dtype=torch.float32, device=dy.device)
+    dw1, db1 = _zeros(w1), torch.zeros(w1.shape[0], dtype=torch.float32, device=dy.device)
     K.gemm_tn(du, x2, dw1, db1)
-    return dxn, dw1, db1, dw2, db2, dres, None, None
+    return dxn, dw1, db1, dw2, db2
+
+
+@mlp_backward.register_fake
+def mlp_backward_fake(dy, xn, w1, w2, h, u, rng, p):
+    f32 = dict(dtype=torch.float32)
+    return (xn.new_empty(xn.shape), w1.new_empty(w1.shape), xn.new_empty(w1.shape[0], **f32), w2.new_empty(w2.shape),
+            xn.new_empty(w2.shape[0], **f32))
+
+
+def _mlp_backward(ctx, dy, _dh, _du):
+    xn, w1, w2, h, u, rng = ctx.saved_tensors
+    dxn, dw1, db1, dw2, db2 = torch.ops.vitpe.mlp_backward(dy, xn, w1, w2, h, u, rng, ctx.p)
+    return dxn, dw1, db1, dw2, db2, dy if ctx.has_resid else None, None, None
 
 
 mlp.register_autograd(_mlp_backward, setup_context=_mlp_setup)
@@ -341,8 +414,8 @@ def dropout(x: Tensor, resid: Optional[Tensor], p: float, rng: Tensor) -> Tensor
 
 
 @dropout.register_fake
-def _(x, resid, p, rng):
-    return torch.empty_like(x)
+def dropout_fake(x, resid, p, rng):
+    return x.new_empty(x.shape)
 
 
 def _drop_setup(ctx, inputs, output):
@@ -351,9 +424,19 @@ def _drop_setup(ctx, inputs, output):
     ctx.p, ctx.has_resid = p, resid is not None
 
 
+@torch.library.custom_op("vitpe::dropout_backward", mutates_args=())
+def dropout_backward(dy: Tensor, rng: Tensor, p: float) -> Tensor:
+    return K.dropout_bwd(dy.contiguous(), rng, p)
+
+
+@dropout_backward.register_fake
+def dropout_backward_fake(dy, rng, p):
+    return dy.new_empty(dy.shape)
+
+
 def _dropout_backward(ctx, dy):
     (rng,) = ctx.saved_tensors
-    return K.dropout_bwd(dy.contiguous(), rng, ctx.p), (dy if ctx.has_resid else None), None, None
+    return torch.ops.vitpe.dropout_backward(dy, rng, ctx.p), (dy if ctx.has_resid else None), None, None
 
 
 dropout.register_autograd(_dropout_backward, setup_context=_drop_setup)
@@ -365,13 +448,23 @@ def drop_path(x: Tensor, resid: Optional[Tensor], p: float, rng: Tensor) -> Tens
 
 
 @drop_path.register_fake
-def _(x, resid, p, rng):
-    return torch.empty_like(x)
+def drop_path_fake(x, resid, p, rng):
+    return x.new_empty(x.shape)
+
+
+@torch.library.custom_op("vitpe::drop_path_backward", mutates_args=())
+def drop_path_backward(dy: Tensor, rng: Tensor, p: float) -> Tensor:
+    return K.drop_path_bwd(dy.contiguous(), rng, p)
+
+
+@drop_path_backward.register_fake
+def drop_path_backward_fake(dy, rng, p):
+    return dy.new_empty(dy.shape)
 
 
 def _drop_path_backward(ctx, dy):
     (rng,) = ctx.saved_tensors
-    return K.drop_path_bwd(dy.contiguous(), rng, ctx.p), (dy if ctx.has_resid else None), None, None
+    return torch.ops.vitpe.drop_path_backward(dy, rng, ctx.p), (dy if ctx.has_resid else None), None, None
 
 
 drop_path.register_autograd(_drop_path_backward, setup_context=_drop_setup)
@@ -394,7 +487,7 @@ def patch_embed(images: Tensor, weight: Tensor, bias: Tensor, cls_token: Tensor,
 
 
 @patch_embed.register_fake
-def _(images, weight, bias, cls_token, ape, patch, bf16):
+def patch_embed_fake(images, weight, bias, cls_token, ape, patch, bf16):
     dt = torch.bfloat16 if bf16 else torch.float32
     B, C, S, _ = images.shape
     P = (S // patch) ** 2
@@ -409,20 +502,34 @@ def _pe_setup(ctx, inputs, output):
     ctx.shapes = (weight.shape, cls_token.shape, None if ape is None else ape.shape)
 
 
-def _pe_backward(ctx, dtok, _dp):
-    (patches,) = ctx.saved_tensors
-    wshape, cshape, ashape = ctx.shapes
+@torch.library.custom_op("vitpe::patch_embed_backward", mutates_args=())
+def patch_embed_backward(dtok: Tensor, patches: Tensor, ape_len: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """-> (dweight [D, C p p], dbias [D], dcls [D], dape [1, ape_len, D]); ape_len 0: no APE table, dape is empty"""
     dev = dtok.device
-    D = wshape[0]
-    B, Ntok, _ = dtok.shape
+    B, Ntok, D = dtok.shape
     dcls = torch.zeros(D, dtype=torch.float32, device=dev)
-    dape = torch.zeros(ashape, dtype=torch.float32, device=dev) if ashape is not None else None
+    dape = torch.zeros((1, ape_len, D), dtype=torch.float32, device=dev) if ape_len > 0 else None
     dape_rows = dape[0, :Ntok - 1] if dape is not None else None  # contiguous leading rows of [1,max_len,D]
     dpatch = K.embed_bwd(dtok.contiguous(), dcls, dape_rows)
     dw = torch.zeros((D, patches.shape[1]), dtype=torch.float32, device=dev)
     db = torch.zeros(D, dtype=torch.float32, device=dev)
     K.gemm_tn(dpatch, patches, dw, db)
-    return None, dw.view(wshape), db, dcls.view(cshape), dape, None, None
+    return dw, db, dcls, dape if dape is not None else dcls.new_empty(0)
+
+
+@patch_embed_backward.register_fake
+def patch_embed_backward_fake(dtok, patches, ape_len):
+    D = dtok.shape[-1]
+    f32 = dict(dtype=torch.float32)
+    return (dtok.new_empty((D, patches.shape[1]), **f32), dtok.new_empty(D, **f32), dtok.new_empty(D, **f32),
+            dtok.new_empty((1, ape_len, D), **f32) if ape_len > 0 else dtok.new_empty(0, **f32))
+
+
+def _pe_backward(ctx, dtok, _dp):
+    (patches,) = ctx.saved_tensors
+    wshape, cshape, ashape = ctx.shapes
+    dw, db, dcls, dape = torch.ops.vitpe.patch_embed_backward(dtok, patches, 0 if ashape is None else ashape[1])
+    return None, dw.view(wshape), db, dcls.view(cshape), None if ashape is None else dape.view(ashape), None, None
 
 
 patch_embed.register_autograd(_pe_backward, setup_context=_pe_setup)
@@ -436,7 +543,7 @@ def head(x: Tensor, gamma: Tensor, beta: Tensor, wh: Tensor, bh: Tensor, eps: fl
 
 
 @head.register_fake
-def _(x, gamma, beta, wh, bh, eps):
+def head_fake(x, gamma, beta, wh, bh, eps):
     B, _, D = x.shape
     f = dict(dtype=torch.float32)
     return x.new_empty((B, wh.shape[0]), **f), x.new_empty((B, D), **f), x.new_empty((B, D), **f), x.new_empty((B,), **f)
@@ -449,12 +556,28 @@ def _head_setup(ctx, inputs, output):
     ctx.xmeta = (x.dtype, x.shape[1])
 
 
+@torch.library.custom_op("vitpe::head_backward", mutates_args=())
+def head_backward(dlogits: Tensor, gamma: Tensor, wh: Tensor, xhat: Tensor, yn: Tensor, rstd: Tensor, bf16: bool, ntok: int
+                  ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (dx [B, ntok, D] in the type of x, dgamma, dbeta, dwh, dbh)"""
+    dtype = torch.bfloat16 if bf16 else torch.float32
+    dwh, dbh = _zeros(wh), torch.zeros(wh.shape[0], dtype=torch.float32, device=wh.device)
+    dg, db = _zeros(gamma), _zeros(gamma)
+    dx = K.head_bwd(dlogits.contiguous().float(), wh.contiguous(), gamma, (xhat, yn, rstd), dtype, ntok, dwh, dbh, dg, db)
+    return dx, dg, db, dwh, dbh
+
+
+@head_backward.register_fake
+def head_backward_fake(dlogits, gamma, wh, xhat, yn, rstd, bf16, ntok):
+    B, D = xhat.shape
+    return (xhat.new_empty((B, ntok, D), dtype=torch.bfloat16 if bf16 else torch.float32), gamma.new_empty(gamma.shape),
+            gamma.new_empty(gamma.shape), wh.new_empty(wh.shape), wh.new_empty(wh.shape[0], dtype=torch.float32))
+
+
 def _head_backward(ctx, dlogits, *_):
     gamma, wh, xhat, yn, rstd = ctx.saved_tensors
     dtype, ntok = ctx.xmeta
-    dwh, dbh = torch.zeros_like(wh), torch.zeros(wh.shape[0], dtype=torch.float32, device=wh.device)
-    dg, db = torch.zeros_like(gamma), torch.zeros_like(gamma)
-    dx = K.head_bwd(dlogits.contiguous().float(), wh.contiguous(), gamma, (xhat, yn, rstd), dtype, ntok, dwh, dbh, dg, db)
+    dx, dg, db, dwh, dbh = torch.ops.vitpe.head_backward(dlogits, gamma, wh, xhat, yn, rstd, dtype == torch.bfloat16, ntok)
     return dx, dg, db, dwh, dbh, None
 
 
@@ -469,8 +592,8 @@ def cross_entropy(logits: Tensor, labels: Tensor) -> Tuple[Tensor, Tensor]:
 
 
 @cross_entropy.register_fake
-def _(logits, labels):
-    return logits.new_empty((), dtype=torch.float32), torch.empty_like(logits, dtype=torch.float32)
+def cross_entropy_fake(logits, labels):
+    return logits.new_empty((), dtype=torch.float32), logits.new_empty(logits.shape, dtype=torch.float32)
 
 
 def _ce_setup(ctx, inputs, output):

@@ -97,16 +97,19 @@ class Attention(nn.Module):
         attention ops for N tokens and the caller's freqs_cis."""
         # RoPE rotates only when the caller passes freqs_cis (reference vit.py:51).  VisionTransformer.forward_features
         # passes a marker and the kernel builds the tables on the device from the module's own parameters (which keeps
-        # the RoPE-mixed frequencies trainable); a caller's own (cos, sin) tensors are used AS GIVEN (vit.py:51-64).
+        # the RoPE-mixed frequencies trainable).  The caller-table rule (vit.py:51): a caller's own (cos, sin) tensors are
+        # used as given, with their own shape ([P, hd/2] or [H, P, hd/2], vit.py:53-64), when and only when
+        # self.pos_encoding is a RoPEAxial / RoPEMixed.  Under every other encoding (None, none, absolute, relative,
+        # polynomial) the reference takes its else branch (vit.py:73-81): freqs_cis is never looked at -- nothing is
+        # rotated, no shape is checked -- and the relative / polynomial bias is still added.
         mode, pe_param, inv_freq, degree, per_head = _pe_args(self.pos_encoding, freqs_cis is not None)
         cos = sin = None
         tables_grad = False
-        if isinstance(freqs_cis, (tuple, list)) and len(freqs_cis) == 2 and all(torch.is_tensor(t) for t in freqs_cis):
+        if isinstance(self.pos_encoding, (RoPEAxial, RoPEMixed)) and isinstance(freqs_cis, (tuple, list)) \
+                and len(freqs_cis) == 2 and all(torch.is_tensor(t) for t in freqs_cis):
             cos, sin = freqs_cis
             if not (cos.is_cuda and sin.is_cuda):
                 raise VitpeError("vitpe: HIP device tensor required (got a CPU tensor; there is no CPU fallback)")
-            if mode in (_MODE["relative"], _MODE["polynomial"]):
-                raise NotImplementedError("vitpe Attention: rotary tables together with an additive bias encoding")
             if cos.shape != sin.shape or cos.dim() not in (2, 3) or tuple(cos.shape[-2:]) != (N - 1, self.head_dim // 2) \
                     or (cos.dim() == 3 and cos.shape[0] != self.num_heads):
                 # (reshape_for_broadcast's error, reference rope_utils.py:39-66)
@@ -302,6 +305,11 @@ class VisionTransformer(nn.Module):
     def forward_features(self, x):
         """[B,C,H,W] -> tokens [B,N,d] after the transformer blocks (reference vit.py:235-271)."""
         require_device(x)
+        if x.requires_grad and torch.is_grad_enabled():
+            # vitpe::patch_embed returns no gradient for `images` (the reference never differentiates them); autograd
+            # would drop it without a word
+            raise NotImplementedError("vitpe VisionTransformer: no gradient w.r.t. the `images` argument of "
+                                      "vitpe::patch_embed (pass images that do not require grad)")
         B, C, H, W = x.shape
         h, w = H // self.patch_size, W // self.patch_size
         ape = self.pos_embed.pos_embed if self.use_pos_embed_in_forward else None
