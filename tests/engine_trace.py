@@ -12,8 +12,9 @@ The trailing stream argument is dropped.  Nothing in the product code knows abou
 CONFIGS are the engine configurations of tests/test_engine_trace_gpu.py and tests/test_engine_route_cpu.py; the golden
 (tests/golden/engine_trace.json) holds per configuration the route flags and per sequence the call names (one string,
 space-separated) and the SHA-256 of the canonical full trace.  The sequences (SEQUENCES) run in order on one engine: `step`,
-`eval`, `parts` always; `probes`, `ema` and `evalloss` (the head's evaluation path: eval_loss and read_metrics) where the
-configuration asks for them.  Run as a script on the GPU:
+`eval`, `parts` always; `probes`, `ema`, `evalloss` (the head's evaluation path: eval_loss and read_metrics) and `evalother`
+(an evaluation forward on a dataset that is not the attached one, then on the attached one) where the configuration asks
+for them.  Run as a script on the GPU:
 
     python tests/engine_trace.py --dump DIR            full traces, one JSON file per configuration and sequence
     python tests/engine_trace.py --write-golden FILE   the golden (only ever from the commit BEFORE an engine refactor)
@@ -51,12 +52,14 @@ BATCH = 2
 
 
 def _cfg(geom="CIFAR", env=None, dtype="bf16", fuse_ln=None, extras=False, model=None, pe="rope-axial", depth=3,
-         dataset=False, probes=False, evalloss=False, optim=None):
-    """evalloss: also trace the head's evaluation path (the `evalloss` sequence).
+         dataset=False, probes=False, evalloss=False, evalother=False, optim=None):
+    """dataset: True attaches a resident dataset and switches augmentation and clipping on; "plain" attaches it alone.
+    evalloss: also trace the head's evaluation path (the `evalloss` sequence).
+    evalother (dataset configurations): also trace forward_indexed on a second dataset (the `evalother` sequence).
     optim: the optimizer-side options, {"clip": max_norm, "ema": (decay, warmup), "groups": vit_param_groups' keywords,
     "sched": set_lr_schedule's arguments}, each applied through the engine's public method when present."""
     return dict(geom=geom, env=env or {}, dtype=dtype, fuse_ln=fuse_ln, extras=extras, model=model or {}, pe=pe, depth=depth,
-                dataset=dataset, probes=probes, evalloss=evalloss, optim=optim or {})
+                dataset=dataset, probes=probes, evalloss=evalloss, evalother=evalother, optim=optim or {})
 
 
 CONFIGS = {"cifar-bf16": _cfg(probes=True, evalloss=True)}
@@ -77,6 +80,13 @@ for _pe in ("absolute", "relative", "polynomial", "rope-axial", "rope-mixed"):
     CONFIGS["pe-" + _pe] = _cfg(pe=_pe)
 CONFIGS["dataset-augment-clip"] = _cfg(dataset=True)
 CONFIGS["depth-1"] = _cfg(depth=1)
+# the input side on its other routes: the uint8 gather as a launch of its own (unfold_u8_aug + gemm_nt + the layernorm_fwd
+# statistics), the fused embed from uint8 without augmentation (no rng_advance), the gather at p = 16 (K = 768: never fused)
+CONFIGS.update({
+    "dataset-unfused": _cfg(dataset=True, env={"VITPE_FUSE_EMBED": "0"}, evalother=True),
+    "dataset-plain": _cfg(dataset="plain", evalother=True),
+    "hd64-dataset": _cfg(geom="HD64", dataset=True, evalother=True),
+})
 # what runs between the backward and the next forward: schedule, clip, AdamW (plain or grouped), EMA, rng_advance
 _OPTIM_ALL = dict(clip=1.0, ema=(0.99, True), groups=dict(no_decay=True, layer_decay=0.75), sched=(1e-3, 40, 5, 1e-5))
 CONFIGS.update({
@@ -197,8 +207,9 @@ def build_engine(cfg):
         ds = ResidentDataset(torch.randint(0, 256, (8, 3, S, S), generator=gen, dtype=torch.uint8),
                              torch.randint(0, 10, (8,), generator=gen), (0.5, 0.5, 0.5), (0.25, 0.25, 0.25))
         eng.attach_dataset(ds)
-        eng.set_augment(4, True)
-        eng.set_grad_clip(1.0)
+        if cfg["dataset"] != "plain":
+            eng.set_augment(4, True)
+            eng.set_grad_clip(1.0)
         idx = torch.tensor([5, 2], device="cuda")
     opt = cfg["optim"]
     if "clip" in opt:
@@ -258,8 +269,25 @@ def _check_evalloss(calls):
     assert len(ctl) == 3 and ctl[0] == ctl[1] != ctl[2], ctl
 
 
+def _seq_evalother(eng, images, labels, idx):
+    """forward_indexed on a second 8-record dataset, then on the attached one: the gather of the first call reads the
+    foreign set's images, the gather of the second the attached set's (checked against the recorder's address table)."""
+    from vitpe import _lib as L
+    from vitpe.data import ResidentDataset
+    gen = torch.Generator().manual_seed(12)
+    S = eng.S
+    other = ResidentDataset(torch.randint(0, 256, (8, 3, S, S), generator=gen, dtype=torch.uint8),
+                            torch.randint(0, 10, (8,), generator=gen), (0.4, 0.4, 0.4), (0.2, 0.2, 0.2))
+    eng.forward_indexed(idx, dataset=other)
+    eng.forward_indexed(idx)
+    rec = L._lib
+    data = [c[3] if c[0] == "patch_embed" else c[2] for c in rec.calls if c[0] in ("patch_embed", "unfold_u8")]
+    want = [rec._addr[t.data_ptr()] for t in (other.images, eng.dataset.images)]
+    assert data == want and want[0] != want[1], (data, want)
+
+
 SEQUENCES = (("step", _seq_step), ("eval", _seq_eval), ("parts", _seq_parts), ("probes", _seq_probes), ("ema", _seq_ema),
-             ("evalloss", _seq_evalloss))
+             ("evalloss", _seq_evalloss), ("evalother", _seq_evalother))
 
 
 def trace_config(name):
@@ -271,7 +299,7 @@ def trace_config(name):
         traces = {}
         for seq, run in SEQUENCES:
             if ((seq == "probes" and not cfg["probes"]) or (seq == "ema" and "ema" not in cfg["optim"])
-                    or (seq == "evalloss" and not cfg["evalloss"])):
+                    or (seq == "evalloss" and not cfg["evalloss"]) or (seq == "evalother" and not cfg["evalother"])):
                 continue
             with recording() as calls:
                 run(eng, images, labels, idx)
