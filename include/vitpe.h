@@ -139,6 +139,30 @@ int vitpe_attention_core_bwd(int dtype, const void* qkv, const void* dout, void*
 int vitpe_attention_core_probs(int dtype, const void* qkv, float* probs, int cls_only, int B, int N, int H, int HD,
                                int mode, const float* cos, const float* sin, const float* table, const float* coeff,
                                int grid, int degree, int coeff_per_head, vitpe_stream_t stream);
+/* vitpe_attention_core_stats: statistics of those probabilities -- models/vit.py:71-84, the tensor `attn` after
+ * `.softmax(dim=-1)` and before `self.attn_drop` -- reduced on the chip, the [N,N] maps never stored: 4 (4 + N) bytes per
+ * (image, head) instead of 4 N^2.  With p the softmax of image b, head h, P = N - 1 and token t >= 1 at the raster position
+ * (y, x) = ((t - 1) / grid, (t - 1) % grid) (any admitted N: the raster may be ragged; grid >= 1 in EVERY mode):
+ *   stats fp32 [B,H,4]
+ *     [VITPE_STAT_DISTANCE]     unit / P . sum_{i>=1} sum_{j>=1} p_ij sqrt((y_i - y_j)^2 + (x_i - x_j)^2)
+ *                               (patch queries and patch keys only, not renormalised: the ViT paper's mean attention
+ *                               distance; unit = patch size gives pixels)
+ *     [VITPE_STAT_ENTROPY]      1 / N . sum_i (- sum_j p_ij ln p_ij)   (nats, 0 ln 0 = 0)
+ *     [VITPE_STAT_CLS_MASS]     1 / P . sum_{i>=1} p_i0
+ *     [VITPE_STAT_CLS_ENTROPY]  - sum_j p_0j ln p_0j
+ *   weights fp32 [B,N], colsum fp32 [B,H,N]: both NULL, or both set: colsum[b,h,j] = sum_i weights[b,i] p_ij, the
+ *     vector-times-map product of attention rollout.  The stats are bitwise the same either way.
+ * Every sum runs in a fixed order without atomics: two calls on the same inputs give the same bits.  Nothing is read at
+ * token rows >= N of qkv or weights, nothing is written outside stats and colsum.  No gradient.  Arguments are checked and
+ * refused exactly as by vitpe_attention_core_fwd (same supported shapes, B == 0 is a no-op); no sync, no allocation.   */
+#define VITPE_STAT_DISTANCE 0
+#define VITPE_STAT_ENTROPY 1
+#define VITPE_STAT_CLS_MASS 2
+#define VITPE_STAT_CLS_ENTROPY 3
+int vitpe_attention_core_stats(int dtype, const void* qkv, float* stats, const float* weights, float* colsum, float unit,
+                               int B, int N, int H, int HD, int mode, const float* cos, const float* sin,
+                               const float* table, const float* coeff, int grid, int degree, int coeff_per_head,
+                               vitpe_stream_t stream);
 /* vitpe_attention_core_bwd_tables: vitpe_attention_core_bwd under RoPE with the CALLER's tables (mode rope-axial: cos / sin
  * [P,HD/2]; rope-mixed: [H,P,HD/2]), which also returns their gradients -- the autograd of the reference's rotation
  * w.r.t. cos and sin as independent inputs (models/rope_utils.py:3-37, models/vit.py:51-68): per rotate-half pair

@@ -1,6 +1,7 @@
 // Kernel templates of the general attention core (attn_core.hip: head dimensions 32 / 64, the C ABI and the fused
 // hd-64 forward; attn_core_hd.hip: the padded head dimensions 24 / 48 and 96 / 128, one translation unit each;
-// attn_core_probs.hip: the softmax probabilities themselves, every head dimension, one translation unit each).
+// attn_core_probs.hip: the softmax probabilities themselves, every head dimension, one translation unit each;
+// attn_core_stats.hip: their statistics reduced on the chip, likewise).
 #pragma once
 #include "attn_common.h"
 #include "philox.h"
@@ -808,6 +809,21 @@ enum { CORE_FWD = 0, CORE_BWD = 1, CORE_PROBS = 2 };
 // VITPE_CORE_HDS x VITPE_CORE_MTS x {bf16, float}; csrc/Makefile's PROBS_HDS) -- everywhere else only this declaration
 template <typename T, int HD, int MT>
 __attribute__((visibility("hidden"))) int launch_core_probs(const AttnArgs& a, hipStream_t s);
+
+// The statistics kernel (attn_core_stats.hip: attn_core_stats_kernel, every head dimension of VITPE_CORE_HDS x
+// VITPE_CORE_MTS x {bf16, float}; csrc/Makefile's STATS_HDS): its arguments wrap AttnArgs, which stays as it is for every
+// other kernel.  stats fp32 [B,H,4] (slots below = include/vitpe.h VITPE_STAT_*); weights fp32 [B,N] and colsum fp32 [B,H,N]
+// both null or both set; unit: what one grid step of the distance is worth.
+struct StatsArgs {
+  AttnArgs a;
+  float* stats;
+  const float* weights;
+  float* colsum;
+  float unit;
+};
+enum { STAT_DISTANCE = 0, STAT_ENTROPY = 1, STAT_CLS_MASS = 2, STAT_CLS_ENTROPY = 3 };
+template <typename T, int HD, int MT>
+__attribute__((visibility("hidden"))) int launch_core_stats(const StatsArgs& sa, hipStream_t s);
 
 template <typename T, int HD>
 __attribute__((visibility("hidden"))) int dispatch_core_t(int op, int MT, const AttnArgs& a, hipStream_t s) {

@@ -341,6 +341,33 @@ extern "C" int vitpe_attention_core_probs(int dtype, const void* qkv, float* pro
                     nullptr, nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr, nullptr, stream, cls_only);
 }
 
+// Statistics of those probabilities, reduced on the chip (attn_core_stats.hip; include/vitpe.h has the definitions): stats
+// fp32 [B,H,4], and with weights [B,N] also colsum [B,H,N] = weights . probs.  Checks and refusals: the forward's, plus
+// grid >= 1 in every mode (the token raster of the distance) and weights / colsum both null or both set.
+extern "C" int vitpe_attention_core_stats(int dtype, const void* qkv, float* stats, const float* weights, float* colsum,
+                                          float unit, int B, int N, int H, int HD, int mode, const float* cos, const float* sin,
+                                          const float* table, const float* coeff, int grid, int degree, int coeff_per_head,
+                                          hipStream_t stream) {
+  const PeArgs pe = {mode, cos, sin, table, coeff, grid, degree, coeff_per_head};
+  VITPE_REQUIRE(qkv && stats && B >= 0 && N >= 2 && H >= 1 && grid >= 1);
+  VITPE_REQUIRE((weights == nullptr) == (colsum == nullptr));
+  VITPE_REQUIRE(pe_ok(pe, N, H, CORE_HMAX));
+  if (B == 0) return 0;
+  StatsArgs sa{};
+  sa.a = attn_args(pe, B, N, H, HD);
+  sa.a.qkv = qkv;
+  sa.stats = stats; sa.weights = weights; sa.colsum = colsum; sa.unit = unit;
+  const int MT = (N + 15) / 16;
+#define VITPE_STATS_MT_CASE(T_, HD_, MT_) if (MT == MT_) return launch_core_stats<T_, HD_, MT_>(sa, stream);
+#define VITPE_STATS_HD_CASE(HD_, OWN_TU_)                                          \
+  if (HD == HD_ && dtype == 1) { VITPE_CORE_MTS(VITPE_STATS_MT_CASE, bf16, HD_) }   \
+  if (HD == HD_ && dtype == 0) { VITPE_CORE_MTS(VITPE_STATS_MT_CASE, float, HD_) }
+  VITPE_CORE_HDS(VITPE_STATS_HD_CASE)
+#undef VITPE_STATS_HD_CASE
+#undef VITPE_STATS_MT_CASE
+  return (int)hipErrorNotSupported;
+}
+
 // Attention-probability dropout inside the core (reference vit.py:84-88, softmax -> attn_drop -> @ v).  p == 0 launches
 // exactly vitpe_attention_core_fwd's kernels.
 extern "C" int vitpe_attention_core_fwd_drop(int dtype, const void* qkv, void* out, int B, int N, int H, int HD, int mode,

@@ -493,6 +493,43 @@ def attention_core_probs(qkv, num_heads, pe: PETables, cls_only=False, out=None)
     return o
 
 
+# slots of attention_core_stats' [B,H,4] result (include/vitpe.h: VITPE_STAT_*)
+STAT_DISTANCE, STAT_ENTROPY, STAT_CLS_MASS, STAT_CLS_ENTROPY = range(4)
+
+
+def attention_core_stats(qkv, num_heads, pe: PETables, unit=1.0, weights=None, out=None):
+    """qkv [B,N,3D] (output of the qkv Linear) -> (stats, colsum): statistics of the attention probabilities
+    softmax(QK^T hd^-0.5 [+ bias]) reduced inside the kernel, the [N,N] maps never stored (vitpe_attention_core_stats).
+    stats fp32 [B,H,4]: STAT_DISTANCE (mean attention distance over patch queries and keys on the pe.grid-wide raster, in
+    units of `unit`), STAT_ENTROPY (mean row entropy, nats), STAT_CLS_MASS (mean attention of the patch queries on the class
+    token), STAT_CLS_ENTROPY (entropy of the class row).  weights fp32 [B,N]: colsum fp32 [B,H,N] = sum_i weights[b,i] p_ij is
+    returned as well (None otherwise); the stats are bitwise the same either way.  out: (stats, colsum_or_None) to write
+    into.  Same operands, supported shapes and refusals as attention_core_fwd; no gradient."""
+    o_stats, o_col = out if out is not None else (None, None)
+    B, N, D3 = qkv.shape
+    HD = D3 // 3 // num_heads
+    # the argument checks come first and look at shapes and dtypes only: they raise before any device is touched
+    if int(pe.grid) < 1:
+        raise L.VitpeError(f"attention_core_stats: grid must be >= 1 (the token raster of the distance), got {pe.grid}")
+    if weights is None and o_col is not None:
+        raise L.VitpeError("attention_core_stats: a colsum output needs weights")
+    if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (B, N)
+                                or not weights.is_contiguous()):
+        raise L.VitpeError(f"attention_core_stats: weights must be float32, contiguous, {(B, N)}")
+    require_device(qkv, weights, o_stats, o_col, pe.cos, pe.sin, pe.table, pe.coeff)
+    if o_stats is None:
+        o_stats = torch.empty((B, num_heads, 4), dtype=torch.float32, device=qkv.device)
+    if weights is not None and o_col is None:
+        o_col = torch.empty((B, num_heads, N), dtype=torch.float32, device=qkv.device)
+    if tuple(o_stats.shape) != (B, num_heads, 4) or o_stats.dtype != torch.float32:
+        raise L.VitpeError(f"attention_core_stats: stats out must be float32 {(B, num_heads, 4)}")
+    if o_col is not None and (tuple(o_col.shape) != (B, num_heads, N) or o_col.dtype != torch.float32):
+        raise L.VitpeError(f"attention_core_stats: colsum out must be float32 {(B, num_heads, N)}")
+    check(lib().vitpe_attention_core_stats(dtype_code(qkv.dtype), ptr(qkv), ptr(o_stats), ptr(weights), ptr(o_col), float(unit),
+                                           B, N, num_heads, HD, *_pe_tail(pe), stream_ptr()), "vitpe_attention_core_stats")
+    return o_stats, o_col
+
+
 def attention_fused64_supported(dtype, N, num_heads, HD) -> bool:
     return bool(lib().vitpe_attention_fused64_supported(dtype_code(dtype), int(N), int(num_heads), int(HD)))
 

@@ -7,6 +7,7 @@ Extension over the reference: `model.set_compute_dtype(torch.bfloat16)` switches
 and GEMM operands to bf16 (fp32 accumulate); the default float32 uses exact-fp32 MFMA and is
 the mode the 1e-4 parity gate runs in.
 """
+import contextlib
 import math
 
 import torch
@@ -166,6 +167,23 @@ class Attention(nn.Module):
             return torch.ops.vitpe.attention_probs(qkv, self.num_heads, mode, int(math.sqrt(N - 1)), pe_param, inv_freq,
                                                    degree, per_head, cos, sin, bool(cls_only))
 
+    def attention_stats(self, x, freqs_cis=None, weights=None, unit=1.0):
+        """Statistics of attention_probs(x, freqs_cis), reduced inside the kernel -- the [N, N] maps are never stored
+        (kernels.attention_core_stats).  -> (stats fp32 [B, H, 4], colsum): the slots kernels.STAT_DISTANCE (mean attention
+        distance on the sqrt(N - 1)-wide token raster, in units of `unit`), STAT_ENTROPY, STAT_CLS_MASS, STAT_CLS_ENTROPY;
+        weights fp32 [B, N]: colsum fp32 [B, H, N] = sum_i weights[b, i] p_ij (what attention rollout needs), else None.
+
+        As attention_probs: the module's own rotation and bias handling, the qkv Linear (with qkv.bias if the module has one)
+        + the statistics kernel of the attention core at every geometry; always the undropped softmax, no RNG drawn, no
+        gradient."""
+        require_device(x, weights)
+        B, N, C = x.shape
+        with torch.no_grad():
+            mode, pe_param, inv_freq, degree, per_head, cos, sin, _ = self._pe_operands(N, freqs_cis)
+            qkv = K.linear(x.contiguous().view(B * N, C), ops._shadow(self.qkv.weight, x.dtype), self.qkv.bias).view(B, N, 3 * C)
+            t = ops._pe_tables(mode, int(math.sqrt(N - 1)), pe_param, inv_freq, degree, per_head, cos, sin)
+            return K.attention_core_stats(qkv, self.num_heads, t, unit=unit, weights=weights)
+
     def _own_mixed_tables(self, cos, sin):
         """Are (cos, sin) provably RoPEMixed.get_freqs_cis of this module's own `freqs` (one _MixedTables node whose
         input is the parameter itself)?"""
@@ -217,6 +235,13 @@ class Block(nn.Module):
         with torch.no_grad():
             n1 = torch.ops.vitpe.layer_norm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)[0]
         return self.attn.attention_probs(n1, freqs_cis=freqs_cis, cls_only=cls_only)
+
+    def attention_stats(self, x, freqs_cis=None, weights=None, unit=1.0):
+        """The attention statistics of this block's forward(x, freqs_cis): Attention.attention_stats on norm1(x)."""
+        require_device(x, weights)
+        with torch.no_grad():
+            n1 = torch.ops.vitpe.layer_norm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)[0]
+        return self.attn.attention_stats(n1, freqs_cis=freqs_cis, weights=weights, unit=unit)
 
     def set_pos_encoding(self, pos_encoding):
         self.attn.set_pos_encoding(pos_encoding)
@@ -376,30 +401,79 @@ class VisionTransformer(nn.Module):
         RNG drawn; the training flags are restored afterwards): the tokens entering block l + 1 are the ordinary eval
         forward's, the probabilities of block l come from Block.attention_probs on its input."""
         require_device(x)
+        want = self._want_layers("attention_maps", layers)
+        with self._eval_no_grad():
+            return {l: blk.attention_probs(t, freqs_cis=freqs_cis, cls_only=cls_only)
+                    for l, blk, t, freqs_cis in self._block_inputs(x, want[-1] if want else -1) if l in want}
+
+    # the analysis methods (attention_maps, attention_stats, attention_rollout) share the next three
+    def _want_layers(self, what, layers):
         depth = len(self.blocks)
         want = list(range(depth)) if layers is None else sorted({int(l) for l in layers})
         if want and not (0 <= want[0] and want[-1] < depth):
-            raise ValueError(f"vitpe attention_maps: layers must be in [0, {depth}), got {list(layers)}")
-        last = want[-1] if want else -1
+            raise ValueError(f"vitpe {what}: layers must be in [0, {depth}), got {list(layers)}")
+        return want
+
+    @contextlib.contextmanager
+    def _eval_no_grad(self):
+        """eval semantics under torch.no_grad(); the training flags are restored afterwards, also on an exception"""
         flags = [(m, m.training) for m in self.modules()]
         self.eval()
         try:
             with torch.no_grad():
-                B, C, H, W = x.shape
-                ape = self.pos_embed.pos_embed if self.use_pos_embed_in_forward else None
-                t = torch.ops.vitpe.patch_embed(x, self.patch_embed.weight, self.patch_embed.bias, self.cls_token, ape,
-                                                self.patch_size, self.compute_dtype == torch.bfloat16)[0]
-                freqs_cis = ((H // self.patch_size) * (W // self.patch_size),) if self.use_rope else None
-                maps = {}
-                for l, blk in enumerate(self.blocks[:last + 1]):
-                    if l in want:
-                        maps[l] = blk.attention_probs(t, freqs_cis=freqs_cis, cls_only=cls_only)
-                    if l < last:
-                        t = blk(t, freqs_cis=freqs_cis)
-                return maps
+                yield
         finally:
             for m, was in flags:
                 m.training = was
+
+    def _block_inputs(self, x, last):
+        """(l, block l, the tokens entering it, freqs_cis) for l = 0 .. last: forward_features' own sequence"""
+        B, C, H, W = x.shape
+        t = self._embed(x)
+        freqs_cis = ((H // self.patch_size) * (W // self.patch_size),) if self.use_rope else None
+        for l, blk in enumerate(self.blocks[:last + 1]):
+            yield l, blk, t, freqs_cis
+            if l < last:
+                t = blk(t, freqs_cis=freqs_cis)
+
+    def attention_stats(self, images, layers=None):
+        """{layer: fp32 [B, H, 4]} of the eval forward of images [B,C,H,W], for the requested layers (default: every block):
+        per head the mean attention distance in pixels (kernels.STAT_DISTANCE; patch queries and keys, unit = patch_size),
+        the mean row entropy in nats (STAT_ENTROPY), the mean attention of the patch queries on the class token
+        (STAT_CLS_MASS) and the entropy of the class row (STAT_CLS_ENTROPY) -- the numbers usually reduced from
+        attention_maps, computed inside the kernel (Block.attention_stats): 16 bytes per (image, head), no [N, N] map is
+        stored.  The contract of attention_maps: eval semantics under torch.no_grad(), no RNG drawn, training flags
+        restored, the tokens entering block l + 1 are the ordinary eval forward's."""
+        require_device(images)
+        want = self._want_layers("attention_stats", layers)
+        with self._eval_no_grad():
+            return {l: blk.attention_stats(t, freqs_cis=freqs_cis, unit=float(self.patch_size))[0]
+                    for l, blk, t, freqs_cis in self._block_inputs(images, want[-1] if want else -1) if l in want}
+
+    def attention_rollout(self, images, start_layer=0, residual=0.5):
+        """Attention rollout (Abnar & Zuidema) of the eval forward of images [B,C,H,W] -> fp32 [B, N]: the class token's row
+        of A^_{L-1} ... A^_{start_layer}, A^_l = (1 - residual) mean_h A_{l,h} + residual I.  Rows of A^ sum to 1, so does
+        the result; [:, 1:] viewed as grid x grid is the rollout map.
+
+        One eval forward keeps every block's input (L B N d elements); then, from the top block down, the row vector
+        v (e_cls to start with) is multiplied into the block's maps inside the statistics kernel (Block.attention_stats with
+        weights=v: colsum = v . A_h per head) and mixed, v <- (1 - residual) mean_h colsum + residual v.  No [N, N] tensor
+        exists at any point.  The contract of attention_maps otherwise."""
+        require_device(images)
+        depth = len(self.blocks)
+        if not 0 <= int(start_layer) < depth:
+            raise ValueError(f"vitpe attention_rollout: start_layer must be in [0, {depth}), got {start_layer}")
+        if not 0.0 <= float(residual) <= 1.0:
+            raise ValueError(f"vitpe attention_rollout: residual must be in [0, 1], got {residual}")
+        with self._eval_no_grad():
+            inputs = [(blk, t, freqs_cis) for _, blk, t, freqs_cis in self._block_inputs(images, depth - 1)]
+            B, N = inputs[0][1].shape[:2]
+            v = torch.zeros(B, N, dtype=torch.float32, device=images.device)
+            v[:, 0] = 1.0
+            for blk, t, freqs_cis in reversed(inputs[int(start_layer):]):
+                colsum = blk.attention_stats(t, freqs_cis=freqs_cis, weights=v)[1]
+                v = (1.0 - residual) * colsum.mean(dim=1) + residual * v
+            return v
 
     def forward(self, x):
         """logits [B,num_classes] fp32 (reference vit.py:273-285); the final LayerNorm is only
