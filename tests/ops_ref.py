@@ -94,15 +94,15 @@ def caller_tables(P, hd, H=None):
     return torch.cos(ang), torch.sin(ang)
 
 
-def pe_leaves(mode, N, H, hd, seed, gain=1.0):
+def pe_leaves(mode, N, H, hd, seed, gain=1.0, degree=3):
     """the positional-encoding operands of a mode (as attn_case in test_kernels_gpu.py); gain: a factor on the bias
-    parameters"""
+    parameters; degree: of the polynomial modes (coefficient k scaled by 8^-k)"""
     pe = {}
     if mode == "relative":
         pe["table"] = rnd(H, 2 * N - 1, seed=seed + 4, scale=0.5 * gain)
     elif mode.startswith("polynomial"):
-        shp = (4,) if mode == "polynomial" else (H, 4)
-        pe["coeff"] = rnd(*shp, seed=seed + 5, scale=0.4 * gain) * torch.tensor([1.0, 1 / 8, 1 / 64, 1 / 512])
+        shp = (degree + 1,) if mode == "polynomial" else (H, degree + 1)
+        pe["coeff"] = rnd(*shp, seed=seed + 5, scale=0.4 * gain) * torch.tensor([1.0 / 8 ** k for k in range(degree + 1)])
     elif mode == "rope-axial":
         pe["inv_freq"] = O.rope_axial_inv_freq(hd, 100.0)
     elif mode == "rope-mixed":
@@ -111,16 +111,17 @@ def pe_leaves(mode, N, H, hd, seed, gain=1.0):
 
 
 @functools.lru_cache(maxsize=None)
-def attn_case(route, mode, resid, tables=None, qkv_bias=False, one_kernel=True):
+def attn_case(route, mode, resid, tables=None, qkv_bias=False, one_kernel=True, degree=3):
     """One attention case: fp32 CPU operands and the geometry.  tables: None | "shared" ([P, hd/2]) | "per_head"
-    ([H, P, hd/2]) constant caller tables (the mode is then the rotary one of that rank, without parameters)."""
+    ([H, P, hd/2]) constant caller tables (the mode is then the rotary one of that rank, without parameters).  degree: of
+    the polynomial modes."""
     dt, N, D, H, want = ROUTES[route]
     hd, B = D // H, B_ATTN
     if tables is not None:
         mode = "rope-axial" if tables == "shared" else "rope-mixed"
     seed = 1000 * (sorted(ROUTES).index(route) + 1) + 10 * ATTN_MODES.index(mode)
     c = types.SimpleNamespace(route=route, dt=dt, N=N, D=D, H=H, hd=hd, B=B, grid=int(math.isqrt(N - 1)), mode=mode,
-                              tables=tables, one_kernel=one_kernel and not qkv_bias)
+                              tables=tables, one_kernel=one_kernel and not qkv_bias, degree=degree)
     assert c.grid * c.grid == N - 1
     c.want_route = want if c.one_kernel else "core"
     got = route_of(dt, N, D, H, one_kernel=c.one_kernel)
@@ -132,10 +133,10 @@ def attn_case(route, mode, resid, tables=None, qkv_bias=False, one_kernel=True):
     c.bproj = rnd(D, seed=seed + 9, scale=0.3)
     c.resid = rnd(B, N, D, seed=seed + 10, scale=0.3) if resid else None   # (small: y stays sensitive to the attention term)
     c.dy = rnd(B, N, D, seed=seed + 3)
-    c.pe = {} if tables is not None else pe_leaves(mode, N, H, hd, seed)
+    c.pe = {} if tables is not None else pe_leaves(mode, N, H, hd, seed, degree=degree)
     c.cos, c.sin = (None, None) if tables is None else caller_tables(N - 1, hd, H if tables == "per_head" else None)
     c.pe_param = c.pe.get("table", c.pe.get("coeff", c.pe.get("freqs")))
-    c.key = (route, mode, resid, tables, qkv_bias, one_kernel)
+    c.key = (route, mode, resid, tables, qkv_bias, one_kernel, degree)
     return c
 
 
@@ -143,18 +144,18 @@ def op_pe_args(c, pe_param=None, cos=None, sin=None):
     """(mode, grid, pe_param, inv_freq, degree, per_head, cos, sin) of the attention ops for a case; the tensor arguments
     default to the case's CPU ones (pass device copies)"""
     poly = c.mode.startswith("polynomial")
-    return (OP_MODE[c.mode], c.grid, pe_param, c.pe.get("inv_freq"), 3 if poly else 0, c.mode == "polynomial_perhead", cos, sin)
+    return (OP_MODE[c.mode], c.grid, pe_param, c.pe.get("inv_freq"), c.degree if poly else 0, c.mode == "polynomial_perhead", cos, sin)
 
 
-def pe_operands64(mode, N, H, pe, cos=None, sin=None):
+def pe_operands64(mode, N, H, pe, cos=None, sin=None, degree=3):
     """(freqs_cis, bias) of the oracle's attention core in float64; pe: {name: float64 leaf}.  The axial tables are
-    built in fp32 like the device's (they are fp32 operands of the kernels, not leaves)."""
+    built in fp32 like the device's (they are fp32 operands of the kernels, not leaves).  degree: of the polynomial modes."""
     if cos is not None:
         return (f64(cos), f64(sin)), None
     if mode == "relative":
         return None, O.relative_bias(pe["table"], N)
     if mode.startswith("polynomial"):
-        return None, O.polynomial_bias(pe["coeff"], N - 1, H, 3, mode == "polynomial")
+        return None, O.polynomial_bias(pe["coeff"], N - 1, H, degree, mode == "polynomial")
     if mode == "rope-axial":
         cos, sin = O.rope_axial_tables(N - 1, pe["inv_freq"].float())
         return (f64(cos), f64(sin)), None
@@ -185,7 +186,7 @@ def attention_operands64(c):
 def _attention_ref(key):
     c = attn_case(*key)
     lv, pe = attention_operands64(c)
-    freqs_cis, bias = pe_operands64(c.mode, c.N, c.H, pe, c.cos, c.sin)
+    freqs_cis, bias = pe_operands64(c.mode, c.N, c.H, pe, c.cos, c.sin, c.degree)
     y = attention_y(lv["xn"], lv["wqkv"], lv["bqkv"], lv["wproj"], lv["bproj"], lv["resid"], c.H, freqs_cis, bias)
     leaves = dict(lv)
     if c.pe_param is not None:
