@@ -163,6 +163,25 @@ int vitpe_attention_core_stats(int dtype, const void* qkv, float* stats, const f
                                int B, int N, int H, int HD, int mode, const float* cos, const float* sin,
                                const float* table, const float* coeff, int grid, int degree, int coeff_per_head,
                                vitpe_stream_t stream);
+/* vitpe_attention_core_relevance: one propagation step of the gradient-weighted attention relevance of Chefer, Gur & Wolf
+ * ("Generic Attention-model Explainability", ICCV 2021), reduced on the chip.  With, for image b and head h,
+ *   A  = models/vit.py:71-84, the tensor `attn` after `.softmax(dim=-1)` and before `self.attn_drop`,
+ *   V  = the head's value rows of qkv (unrotated), dO = the head's columns of dout [B,N,H HD], the gradient of a scalar
+ *        w.r.t. the merged-head output of the core (the tensor in front of proj),
+ *   G  = dO V^T [N,N] = the gradient w.r.t. A with V held fixed (what a backward hook on `attn` sees; NOT the gradient
+ *        w.r.t. the logits),
+ *   colsum fp32 [B,H,N]:  colsum[b,h,j] = sum_i weights[b,i] f(G_ij A_ij),   f = max(0, .) if clamp != 0, else f(x) = x.
+ * weights fp32 [B,N] is required.  Neither A nor G is stored.  qkv and dout have the compute type (fp32 accumulation of
+ * G on the matrix core).  Every sum runs in a fixed order without atomics: two calls on the same inputs give the same
+ * bits.  Nothing is read at token rows >= N, a padding query or key contributes exactly 0, nothing is written outside
+ * colsum.  No gradient.  Arguments are checked as by vitpe_attention_core_fwd (B == 0 is a no-op).  Supported shapes:
+ * those of vitpe_attention_core_fwd whose K~ and V tiles and reduction slabs fit the 160 KB LDS together (DESIGN.md,
+ * "Attention relevance", lists the refused ones); hipErrorNotSupported otherwise, the outputs untouched.  No sync, no
+ * allocation.   */
+int vitpe_attention_core_relevance(int dtype, const void* qkv, const void* dout, const float* weights, float* colsum,
+                                   int clamp, int B, int N, int H, int HD, int mode, const float* cos, const float* sin,
+                                   const float* table, const float* coeff, int grid, int degree, int coeff_per_head,
+                                   vitpe_stream_t stream);
 /* vitpe_attention_core_bwd_tables: vitpe_attention_core_bwd under RoPE with the CALLER's tables (mode rope-axial: cos / sin
  * [P,HD/2]; rope-mixed: [H,P,HD/2]), which also returns their gradients -- the autograd of the reference's rotation
  * w.r.t. cos and sin as independent inputs (models/rope_utils.py:3-37, models/vit.py:51-68): per rotate-half pair

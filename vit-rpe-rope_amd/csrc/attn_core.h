@@ -1,7 +1,8 @@
 // Kernel templates of the general attention core (attn_core.hip: head dimensions 32 / 64, the C ABI and the fused
 // hd-64 forward; attn_core_hd.hip: the padded head dimensions 24 / 48 and 96 / 128, one translation unit each;
 // attn_core_probs.hip: the softmax probabilities themselves, every head dimension, one translation unit each;
-// attn_core_stats.hip: their statistics reduced on the chip, likewise).
+// attn_core_stats.hip: their statistics reduced on the chip, likewise; attn_core_relevance.hip: the gradient-weighted
+// relevance product, likewise).
 #pragma once
 #include "attn_common.h"
 #include "philox.h"
@@ -824,6 +825,19 @@ struct StatsArgs {
 enum { STAT_DISTANCE = 0, STAT_ENTROPY = 1, STAT_CLS_MASS = 2, STAT_CLS_ENTROPY = 3 };
 template <typename T, int HD, int MT>
 __attribute__((visibility("hidden"))) int launch_core_stats(const StatsArgs& sa, hipStream_t s);
+
+// The relevance kernel (attn_core_relevance.hip: attn_core_relevance_kernel, the same instantiation list; csrc/Makefile's
+// RELEVANCE_HDS): its arguments wrap AttnArgs likewise (a.qkv and a.dout set).  weights fp32 [B,N], colsum fp32 [B,H,N] =
+// sum_i weights_i f(G_ij A_ij) with G = dO V^T; clamp: f = max(0, .), else the identity.  The kernel has its own LDS fit
+// rule (it stages V beside K~): hipErrorNotSupported where it fails.
+struct RelevanceArgs {
+  AttnArgs a;
+  const float* weights;
+  float* colsum;
+  int clamp;
+};
+template <typename T, int HD, int MT>
+__attribute__((visibility("hidden"))) int launch_core_relevance(const RelevanceArgs& ra, hipStream_t s);
 
 template <typename T, int HD>
 __attribute__((visibility("hidden"))) int dispatch_core_t(int op, int MT, const AttnArgs& a, hipStream_t s) {

@@ -368,6 +368,32 @@ extern "C" int vitpe_attention_core_stats(int dtype, const void* qkv, float* sta
   return (int)hipErrorNotSupported;
 }
 
+// Gradient-weighted attention relevance (attn_core_relevance.hip; include/vitpe.h has the definitions): colsum fp32
+// [B,H,N] = sum_i weights_i f(G_ij A_ij), G = dout_h V_h^T, f = max(0, .) under clamp.  Checks: the forward's, plus dout,
+// weights and colsum all set.  Refusals: the forward's, plus the geometries whose K~ + V + slabs do not fit the LDS.
+extern "C" int vitpe_attention_core_relevance(int dtype, const void* qkv, const void* dout, const float* weights,
+                                              float* colsum, int clamp, int B, int N, int H, int HD, int mode,
+                                              const float* cos, const float* sin, const float* table, const float* coeff,
+                                              int grid, int degree, int coeff_per_head, hipStream_t stream) {
+  const PeArgs pe = {mode, cos, sin, table, coeff, grid, degree, coeff_per_head};
+  VITPE_REQUIRE(qkv && dout && weights && colsum && B >= 0 && N >= 2 && H >= 1);
+  VITPE_REQUIRE(pe_ok(pe, N, H, CORE_HMAX));
+  if (B == 0) return 0;
+  RelevanceArgs ra{};
+  ra.a = attn_args(pe, B, N, H, HD);
+  ra.a.qkv = qkv; ra.a.dout = dout;
+  ra.weights = weights; ra.colsum = colsum; ra.clamp = clamp != 0;
+  const int MT = (N + 15) / 16;
+#define VITPE_RELEVANCE_MT_CASE(T_, HD_, MT_) if (MT == MT_) return launch_core_relevance<T_, HD_, MT_>(ra, stream);
+#define VITPE_RELEVANCE_HD_CASE(HD_, OWN_TU_)                                          \
+  if (HD == HD_ && dtype == 1) { VITPE_CORE_MTS(VITPE_RELEVANCE_MT_CASE, bf16, HD_) }   \
+  if (HD == HD_ && dtype == 0) { VITPE_CORE_MTS(VITPE_RELEVANCE_MT_CASE, float, HD_) }
+  VITPE_CORE_HDS(VITPE_RELEVANCE_HD_CASE)
+#undef VITPE_RELEVANCE_HD_CASE
+#undef VITPE_RELEVANCE_MT_CASE
+  return (int)hipErrorNotSupported;
+}
+
 // Attention-probability dropout inside the core (reference vit.py:84-88, softmax -> attn_drop -> @ v).  p == 0 launches
 // exactly vitpe_attention_core_fwd's kernels.
 extern "C" int vitpe_attention_core_fwd_drop(int dtype, const void* qkv, void* out, int B, int N, int H, int HD, int mode,

@@ -530,6 +530,39 @@ def attention_core_stats(qkv, num_heads, pe: PETables, unit=1.0, weights=None, o
     return o_stats, o_col
 
 
+def attention_core_relevance(qkv, dout, num_heads, pe: PETables, weights, clamp=True, out=None):
+    """One propagation step of the gradient-weighted attention relevance (Chefer, Gur & Wolf, ICCV 2021), reduced inside
+    the kernel (vitpe_attention_core_relevance): qkv [B,N,3D] (output of the qkv Linear), dout [B,N,D] (the gradient of a
+    scalar w.r.t. the core's merged-head output, the tensor in front of proj; same dtype as qkv), weights fp32 [B,N]
+    -> colsum fp32 [B,H,N] = sum_i weights[b,i] f(G_ij A_ij), with A the attention probabilities
+    (attention_core_probs), G = dout_h V_h^T their gradient with V held fixed, f = max(0, .) under clamp (Chefer's rule) and
+    the identity without.  Neither [N,N] tensor is stored; fixed summation order (two calls give the same bits).  out: the
+    colsum to write into.  The operands of attention_core_fwd; refused beyond its refusals: the geometries whose K~ and V
+    tiles do not fit the LDS together ("Attention relevance").  No gradient."""
+    # the argument checks come first and look at shapes and dtypes only: they raise before any device is touched
+    if qkv.dim() != 3 or qkv.shape[-1] % (3 * num_heads) != 0:
+        raise L.VitpeError(f"attention_core_relevance: qkv must be [B, N, 3 * H * hd], got {tuple(qkv.shape)}")
+    B, N, D3 = qkv.shape
+    D = D3 // 3
+    HD = D // num_heads
+    if qkv.dtype not in (torch.float32, torch.bfloat16) or not qkv.is_contiguous():
+        raise L.VitpeError("attention_core_relevance: qkv must be float32 or bfloat16, contiguous")
+    if dout is None or tuple(dout.shape) != (B, N, D) or dout.dtype != qkv.dtype or not dout.is_contiguous():
+        raise L.VitpeError(f"attention_core_relevance: dout must be {qkv.dtype}, contiguous, {(B, N, D)}")
+    if weights is None:
+        raise L.VitpeError("attention_core_relevance: weights are required")
+    if weights.dtype != torch.float32 or tuple(weights.shape) != (B, N) or not weights.is_contiguous():
+        raise L.VitpeError(f"attention_core_relevance: weights must be float32, contiguous, {(B, N)}")
+    if out is not None and (tuple(out.shape) != (B, num_heads, N) or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise L.VitpeError(f"attention_core_relevance: colsum out must be float32, contiguous, {(B, num_heads, N)}")
+    require_device(qkv, dout, weights, out, pe.cos, pe.sin, pe.table, pe.coeff)
+    o = out if out is not None else torch.empty((B, num_heads, N), dtype=torch.float32, device=qkv.device)
+    check(lib().vitpe_attention_core_relevance(dtype_code(qkv.dtype), ptr(qkv), ptr(dout), ptr(weights), ptr(o),
+                                               int(bool(clamp)), B, N, num_heads, HD, *_pe_tail(pe), stream_ptr()),
+          "vitpe_attention_core_relevance")
+    return o
+
+
 def attention_fused64_supported(dtype, N, num_heads, HD) -> bool:
     return bool(lib().vitpe_attention_fused64_supported(dtype_code(dtype), int(N), int(num_heads), int(HD)))
 

@@ -184,6 +184,31 @@ class Attention(nn.Module):
             t = ops._pe_tables(mode, int(math.sqrt(N - 1)), pe_param, inv_freq, degree, per_head, cos, sin)
             return K.attention_core_stats(qkv, self.num_heads, t, unit=unit, weights=weights)
 
+    def attention_relevance(self, x, dy, freqs_cis=None, weights=None, clamp=True):
+        """One step of the gradient-weighted attention relevance (Chefer, Gur & Wolf, ICCV 2021) of forward(x, freqs_cis),
+        reduced inside the kernel -- neither the [N, N] probabilities A nor their gradient G is stored
+        (kernels.attention_core_relevance).  x: forward's input; dy [B, N, C]: the gradient of a scalar w.r.t. forward's
+        output (x's dtype); weights fp32 [B, N], default e_cls (1 on the class token).
+        -> colsum fp32 [B, H, N] = sum_i weights[b, i] f(G_ij A_ij) with G = dO_h V_h^T, dO = dy W_proj the gradient w.r.t. the
+        merged-head output in front of proj (the proj bias plays no part), V the head's value rows of the qkv projection
+        (unrotated, with qkv.bias if the module has one), f = max(0, .) under clamp and the identity without.
+
+        As attention_stats: the module's own rotation and bias handling, the qkv Linear + the relevance kernel of the
+        attention core at every geometry it fits; always the undropped softmax, no RNG drawn, no gradient."""
+        require_device(x, dy, weights)
+        B, N, C = x.shape
+        if tuple(dy.shape) != (B, N, C) or dy.dtype != x.dtype:
+            raise VitpeError(f"vitpe attention_relevance: dy must be {x.dtype} {(B, N, C)}")
+        with torch.no_grad():
+            mode, pe_param, inv_freq, degree, per_head, cos, sin, _ = self._pe_operands(N, freqs_cis)
+            qkv = K.linear(x.contiguous().view(B * N, C), ops._shadow(self.qkv.weight, x.dtype), self.qkv.bias).view(B, N, 3 * C)
+            dout = K.linear(dy.contiguous().view(B * N, C), ops._shadow_t(self.proj.weight, x.dtype), None).view(B, N, C)
+            t = ops._pe_tables(mode, int(math.sqrt(N - 1)), pe_param, inv_freq, degree, per_head, cos, sin)
+            if weights is None:
+                weights = torch.zeros(B, N, dtype=torch.float32, device=x.device)
+                weights[:, 0] = 1.0
+            return K.attention_core_relevance(qkv, dout, self.num_heads, t, weights, clamp=clamp)
+
     def _own_mixed_tables(self, cos, sin):
         """Are (cos, sin) provably RoPEMixed.get_freqs_cis of this module's own `freqs` (one _MixedTables node whose
         input is the parameter itself)?"""
@@ -242,6 +267,14 @@ class Block(nn.Module):
         with torch.no_grad():
             n1 = torch.ops.vitpe.layer_norm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)[0]
         return self.attn.attention_stats(n1, freqs_cis=freqs_cis, weights=weights, unit=unit)
+
+    def attention_relevance(self, x, dmid, freqs_cis=None, weights=None, clamp=True):
+        """The relevance step of this block's forward(x, freqs_cis): Attention.attention_relevance on norm1(x).  dmid: the
+        gradient at the block's x + attn(norm1(x)), which is the gradient of the attention branch's output."""
+        require_device(x, dmid, weights)
+        with torch.no_grad():
+            n1 = torch.ops.vitpe.layer_norm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)[0]
+        return self.attn.attention_relevance(n1, dmid, freqs_cis=freqs_cis, weights=weights, clamp=clamp)
 
     def set_pos_encoding(self, pos_encoding):
         self.attn.set_pos_encoding(pos_encoding)
@@ -474,6 +507,68 @@ class VisionTransformer(nn.Module):
                 colsum = blk.attention_stats(t, freqs_cis=freqs_cis, weights=v)[1]
                 v = (1.0 - residual) * colsum.mean(dim=1) + residual * v
             return v
+
+    def attention_relevance(self, images, target=None, start_layer=0, clamp=True):
+        """Gradient-weighted attention relevance (Chefer, Gur & Wolf, "Generic Attention-model Explainability", ICCV 2021) of
+        the eval forward of images [B,C,H,W] for the class target_b of each image -> fp32 [B, N]: the class token's row of
+        R = (I + A~_{L-1}) ... (I + A~_{start_layer}),  A~_l = mean_h f(G_{l,h} . A_{l,h}),  with A the attention
+        probabilities, G = d logits[b, target_b] / dA (the value rows held fixed: what a backward hook on the softmax sees)
+        and f = max(0, .) under clamp (Chefer's rule), the signed product without.  target: LongTensor [B], or None = the
+        arg-max class of each image.  [:, 1:] viewed as grid x grid is the relevance map; [:, 0] is returned as it is: the
+        identity's 1 plus the class token's own relevance.
+
+        One eval pass from the embedded tokens under enable_grad -- Block.forward's eval sequence, op for op -- keeps each
+        block's norm1 output and its x + attn(norm1(x)); torch.autograd.grad w.r.t. the latter gives the gradient of every
+        attention branch in one backward.  Then, from the top block down, the row vector v (e_cls to start with) goes
+        through the relevance kernel (Attention.attention_relevance with weights=v) and v <- v + mean_h colsum.  No [N, N]
+        tensor exists at any point.  saliency's contract: eval semantics (no dropout, no stochastic depth, no RNG drawn;
+        the training flags are restored afterwards, also on an exception), no parameter's .grad is created or changed,
+        `images` is left as it is, the result carries no graph."""
+        depth = len(self.blocks)
+        if not 0 <= int(start_layer) < depth:
+            raise ValueError(f"vitpe attention_relevance: start_layer must be in [0, {depth}), got {start_layer}")
+        if target is not None and (not torch.is_tensor(target) or target.dtype != torch.int64
+                                   or tuple(target.shape) != (images.shape[0],)):
+            raise ValueError("vitpe attention_relevance: target must be a LongTensor [B]")
+        require_device(images)
+        flags = [(m, m.training) for m in self.modules()]
+        self.eval()
+        try:
+            logits, kept, freqs_cis = self._relevance_pass(images)
+            with torch.enable_grad():
+                if target is None:
+                    target = logits.detach().argmax(dim=1)
+                picked = logits.gather(1, target.to(logits.device).view(-1, 1)).sum()
+                kept = kept[int(start_layer):]
+                dmids = torch.autograd.grad(picked, inputs=[x_mid for _, _, x_mid in kept])
+            with torch.no_grad():
+                B, N = kept[0][1].shape[:2]
+                v = torch.zeros(B, N, dtype=torch.float32, device=images.device)
+                v[:, 0] = 1.0
+                for (blk, n1, _), dmid in zip(reversed(kept), reversed(dmids)):
+                    v = v + blk.attn.attention_relevance(n1, dmid, freqs_cis=freqs_cis, weights=v, clamp=clamp).mean(dim=1)
+                return v
+        finally:
+            for m, was in flags:
+                m.training = was
+
+    def _relevance_pass(self, images):
+        """(logits with their graph, [(block, norm1 output detached, x + attn(norm1 x))] bottom block first, freqs_cis):
+        forward's own ops from the embedded tokens on, under enable_grad; the caller has set eval mode."""
+        B, C, H, W = images.shape
+        with torch.no_grad():
+            tok = self._embed(images.detach())
+        freqs_cis = ((H // self.patch_size) * (W // self.patch_size),) if self.use_rope else None
+        kept = []
+        with torch.enable_grad():
+            x = tok.requires_grad_(True)
+            for blk in self.blocks:   # Block.forward, eval branch
+                n1 = torch.ops.vitpe.layer_norm(x, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps)[0]
+                x_mid = blk.attn(n1, freqs_cis=freqs_cis, resid=x)
+                n2 = torch.ops.vitpe.layer_norm(x_mid, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)[0]
+                x = blk.mlp(n2, resid=x_mid)
+                kept.append((blk, n1.detach(), x_mid))
+            return self._head(x), kept, freqs_cis
 
     def forward(self, x):
         """logits [B,num_classes] fp32 (reference vit.py:273-285); the final LayerNorm is only
